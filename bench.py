@@ -28,11 +28,17 @@ GB/s field is executed bytes over measured time, so none can exceed the 8 TB/s p
 enters only as the dimensionless ``survey_model_time_ratio``: the time that model's bytes take at
 the 8 TB/s peak over the measured step time (> 1: the step is faster than a 4-pass CGS2 could be
 even at roofline).  ``roofline`` is the dominant kernel family timed live with HIP events on the
-launch stream.  Outside the timed region: ``restart`` times one
+launch stream, inside the timed steps.
+
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps, writes the
+last step's outputs if ``--dump-outputs DIR`` is given (``dump_outputs``) and prints the line.
+``--full`` adds, outside the timed region: ``restart`` times one
 Krylov–Schur condensation of the final factorisation (H rescaled to unit spectral radius, see
-there), ``krylov_schur_leg`` runs config 3's Krylov–Schur (k_dim=m, schur_tgt=4) and
+there), ``krylov_schur_leg`` runs config 3's Krylov–Schur (k_dim=m, schur_tgt=4),
 ``krylov_schur_restart_leg`` the same on a clustered time-stepper-like spectrum that needs real
-m-column restarts.
+m-column restarts, and the three CPU lines (``cpu_baseline``, ``cpu_baseline_1core``,
+``cpu_optimised``) are timed on the host; ``--no-restart`` / ``--no-ks`` / ``--no-cpu`` drop one of
+them again.  Without ``--full`` those fields of the line are null.
 """
 from __future__ import annotations
 
@@ -438,9 +444,15 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-E", type=int, default=2000,
                     help="CPU baseline sample: one full factorisation on all threads (2,000 -> N=4.5e6, ~20 s)")
     ap.add_argument("--cpu-E-1core", type=int, default=128, help="... with one thread (128 -> N=2.9e5)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-restart", action="store_true", help="skip the restart-rotation measurement")
-    ap.add_argument("--no-ks", action="store_true", help="skip the Krylov–Schur restart leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: the restart-rotation "
+                         "measurement, the two Krylov–Schur legs and the CPU baselines (minutes; off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float64; "
+                         "rank 0's shard at world > 1), see dump_outputs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-restart", action="store_true", help="with --full: skip the restart-rotation measurement")
+    ap.add_argument("--no-ks", action="store_true", help="with --full: skip the Krylov–Schur legs")
     ap.add_argument("--force-collectives", action="store_true",
                     help="at one GPU, route every partial through a world-1 RCCL group (collective cost)")
     ap.add_argument("--dry-launch", action="store_true",
@@ -451,7 +463,10 @@ def parse_args(argv=None):
     ap.add_argument("--collective-probe", action="store_true",
                     help="CPU test of the collective path: init the process group (bounded timeout, rank "
                          "watchdog), gather the ranks' device identities, one all-reduce, print one JSON line")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -628,7 +643,7 @@ def run(args):
     d, exact = syn.laplacian_shift_invert(lay)
     op = DiagOperator(ctx, d)
     rho = float(np.abs(exact[0]))
-    d_scaled = d / rho
+    d_scaled = d / rho if args.full and not args.no_ks else None   # the Krylov–Schur leg's operator
     del d
     seed = ctx.vector()
     seed.fill_hash(11)
@@ -642,7 +657,7 @@ def run(args):
         H = Hd.download()
         vals, vecs = lapack.eig(H[:m, :m])
         res = np.abs(H[m, m - 1] * vecs[m - 1, :])
-        return vals, res
+        return vals, res, H
 
     for _ in range(args.warmup):
         one_step()
@@ -653,7 +668,7 @@ def run(args):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        vals, res = one_step()
+        vals, res, H_last = one_step()
     torch.cuda.synchronize(dev)
     comm.barrier()
     elapsed = time.perf_counter() - t0
@@ -664,12 +679,14 @@ def run(args):
     last_step_ms = (sum(timer.last_ms(k) for k in ("block_dot2", "dcgs2_update"))
                     if args.mode in ("dcgs2", "mgs2-lagged") else None)
     ctx.check_nan()
+    if args.dump_outputs and rank == 0:   # before --full's restart leg rotates Q in place
+        dump_outputs(args.dump_outputs, vals, res, H_last, Q, m)
 
     # Krylov–Schur restart on the final factorisation (outside the timed region; reported beside
     # the metric): the kept-column rotation the solver runs, and the reference's
     # full k-column rotation priced against the fp64 matrix peak.
     restart = None
-    if not args.no_restart:
+    if args.full and not args.no_restart:
         rt = PhaseTimer(dev)
         ctx.timer = rt
         # the shift-invert spectrum is not inside the unit disc (every |mu| >= 1 - schur_del would be
@@ -727,7 +744,7 @@ def run(args):
                         "rotate_wide_frac_hbm": round(wp["gbps"] / HBM_PEAK_GBS, 4),
                         "rotate_wide_tflops": round(2.0 * lay.N * m * n_w / (wp["avg_ms"] * 1e-3) / 1e12, 2)})
     ks_leg = ks_restart = None
-    if not args.no_ks:
+    if args.full and not args.no_ks:
         ks_leg = krylov_schur_leg(ctx, lay, Q, d_scaled, exact / rho, seed, m, 4)
         del d_scaled
         # the same m and schur_tgt on a time-stepper-like clustered spectrum: real m-column restarts
@@ -743,6 +760,32 @@ def run(args):
     out = bench_line(args, comm, glay, lay, m, elapsed, phases, last_step_ms, vals, res, exact, restart, ks_leg,
                      ks_restart, devices, dev)
     finish(args, comm, out, m)
+
+
+DUMP_BASIS_ROWS = 16384   # sampled rows of the basis in --dump-outputs ((m+1) x 16384 doubles: 17 MB at m=128)
+
+
+def dump_outputs(out_dir, vals, res, H, Q, m) -> None:
+    """``--dump-outputs DIR``: what the last timed step returned to its caller, as float64 ``.npy``
+    files (under 20 MB in all at the default size), for comparing two builds output for output.
+    The inputs (hashed seed, synthetic operator, weights) depend only on the arguments.
+
+    * ``ritz_values.npy`` (m, 2): real and imaginary parts of the Ritz values, in LAPACK's order;
+    * ``ritz_residuals.npy`` (m,): |H[m, m-1] y_m| per Ritz pair;
+    * ``hessenberg.npy`` (m+1, m): the Hessenberg matrix of the factorisation;
+    * ``basis_sample.npy`` (m+1, n): the Krylov basis Q (this rank's shard) at n <= 16384 fixed
+      storage rows, drawn once with a seeded generator, and ``basis_sample_rows.npy`` (n,): those
+      rows as float64 (exact: they are below 2^53)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    ld = Q.storage.shape[1]
+    rows = np.unique(np.random.default_rng(20240531).integers(0, ld, size=min(DUMP_BASIS_ROWS, ld)))
+    sample = torch.index_select(Q.storage[:m + 1], 1, torch.as_tensor(rows, device=Q.storage.device)).cpu().numpy()
+    arrays = {"ritz_values": np.stack([vals.real, vals.imag], axis=1), "ritz_residuals": res,
+              "hessenberg": H[:m + 1, :m], "basis_sample": sample, "basis_sample_rows": rows}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def bench_line(args, comm, glay, lay, m, elapsed, phases, last_step_ms, vals, res, exact, restart, ks_leg,
@@ -816,6 +859,7 @@ def bench_line(args, comm, glay, lay, m, elapsed, phases, last_step_ms, vals, re
         "distinct_devices": distinct_devices(devices),
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(ms_per_step, 3),
         "survey_model_time_ratio": round(survey_time_ratio, 3),
         "higher_is_better": True,
@@ -871,12 +915,12 @@ def bench_line(args, comm, glay, lay, m, elapsed, phases, last_step_ms, vals, re
 
 def finish(args, comm, out, m) -> None:
     """Every rank leaves the process group together; the ranks other than 0 end there.  Rank 0 then
-    times the CPU lines (unless --no-cpu) — at every world size, with no peer left waiting in a
-    collective — and prints the ONE JSON line."""
+    times the CPU lines (with --full, unless --no-cpu) — at every world size, with no peer left
+    waiting in a collective — and prints the ONE JSON line."""
     rank, world = comm.rank, comm.world
     _leave_group(comm, keep_rank0=True)
     if rank == 0:
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             out.update(host_baselines(args, m, out["ms_per_step"]))
         print(json.dumps(out), file=args.json_out, flush=True)
     args.json_out.flush()

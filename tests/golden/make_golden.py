@@ -11,8 +11,10 @@ Provenance, per fixture:
   Data held by the reference itself: these pin the product's ``.fld`` reader.
 * ``bf_1cyl0_seed.npz`` — the cylinder base flow (U, V and P mapped to the lx2 mesh) of
   ``BF_1cyl0.f00001`` as one state vector on the real cylinder mesh (E=1996, N=175,648, reference
-  order), the seed of the config-2 golden run; lets the GPU box run on the reference's own data
-  without ``/root/reference``.
+  order), the seed of the config-2 golden run.
+* ``reference_fld/`` — those four base-flow files themselves, byte for byte, as xz pieces of at most
+  1.5 MB of file each (``pack_reference``; ``tests/helpers.py`` ``reference_file`` unpacks them), so
+  that the reader tests and this script need no checkout of the reference.
 * ``ks_*.npz`` / ``gmres_*.npz`` — outputs of the CPU oracle (``oracle/``: the C restatement of
   ``update_hessenberg_matrix`` and the numpy restatement of the drivers) on the synthetic BASELINE
   operators, with the dense steps on Intel MKL (``oracle/mkl_lapack.py``, the LAPACK the
@@ -37,11 +39,13 @@ Provenance, per fixture:
 
 usage: python tests/golden/make_golden.py        (writes next to this file)
        python tests/golden/make_golden.py --only-solvers   (the LAPACK-dependent fixtures only)
+       python tests/golden/make_golden.py --pack-reference DIR   (reference_fld/ from a reference checkout DIR)
 """
 from __future__ import annotations
 
 import hashlib
 import json
+import lzma
 import os
 import struct
 import sys
@@ -54,13 +58,31 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-REF = "/root/reference"
+PACK_PIECE = 1_500_000   # bytes of file per committed xz piece (each piece well under 1 MiB)
 FLD_FILES = [
     "examples/cylinder/BF_1cyl0.f00001",
     "examples/cylinder/BFRe40_1cyl0.f00001",
     "examples/back_fstep/baseflow/BF_bfs0.f00001",
     "examples/back_fstep/transient_growth/BF_bfs0.f00001",
 ]
+
+
+def _ref(rel):
+    from helpers import reference_file
+
+    return reference_file(rel)
+
+
+def pack_reference(src_root):
+    """Write reference_fld/<rel with / as __>.<k>.xz from the files under ``src_root``."""
+    from helpers import REFERENCE_FLD_DIR, _packed_name
+
+    os.makedirs(REFERENCE_FLD_DIR, exist_ok=True)
+    for rel in FLD_FILES:
+        raw = open(os.path.join(src_root, rel), "rb").read()
+        for k in range(0, len(raw), PACK_PIECE):
+            with open(os.path.join(REFERENCE_FLD_DIR, f"{_packed_name(rel)}.{k // PACK_PIECE}.xz"), "wb") as fh:
+                fh.write(lzma.compress(raw[k:k + PACK_PIECE], preset=9 | lzma.PRESET_EXTREME))
 
 
 def _parse_std(path):
@@ -95,10 +117,10 @@ def _parse_std(path):
 def gen_fld():
     out = {}
     for rel in FLD_FILES:
-        tok, tag, emap, fields = _parse_std(os.path.join(REF, rel))
+        tok, tag, emap, fields = _parse_std(_ref(rel))
         out[rel] = {
             "header_tokens": tok[:12],
-            "size_bytes": os.path.getsize(os.path.join(REF, rel)),
+            "size_bytes": os.path.getsize(_ref(rel)),
             "endian_tag": tag,
             "emap_sum": int(emap.sum()), "emap_first": emap[:8].tolist(),
             "emap_sha1": hashlib.sha1(emap.astype("<i8").tobytes()).hexdigest(),
@@ -178,7 +200,7 @@ def gen_solvers():
     L = olayout(lay)
     w = syn.mass_weights(lay)
     if not os.path.exists(os.path.join(HERE, "bf_1cyl0_seed.npz")):   # frozen once written
-        f = fld.read_fld(os.path.join(REF, FLD_FILES[0]))
+        f = fld.read_fld(_ref(FLD_FILES[0]))
         bf = syn.to_reference_order(lay, fld.vector_from_fld(lay, f))
         np.savez_compressed(os.path.join(HERE, "bf_1cyl0_seed.npz"), seed_ref=bf)
     bf = np.load(os.path.join(HERE, "bf_1cyl0_seed.npz"))["seed_ref"]
@@ -342,7 +364,7 @@ def gen_noise():
     points) as checksums and every 97th value."""
     import oracle as orc
 
-    _, _, emap, fields = _parse_std(os.path.join(REF, FLD_FILES[0]))
+    _, _, emap, fields = _parse_std(_ref(FLD_FILES[0]))
     order = np.argsort(emap)
     x, y = fields["x"][order].ravel(), fields["y"][order].ravel()
     np.savez_compressed(os.path.join(HERE, "cyl_mesh_xy.npz"), x=x, y=y)
@@ -398,13 +420,16 @@ def gen_ordering():
 
 
 if __name__ == "__main__":
-    if "--only-wavemaker" in sys.argv:   # needs only the committed bf_1cyl0_seed.npz, not /root/reference
+    if "--pack-reference" in sys.argv:
+        pack_reference(sys.argv[sys.argv.index("--pack-reference") + 1])
+        sys.exit(0)
+    if "--only-wavemaker" in sys.argv:   # needs only the committed bf_1cyl0_seed.npz
         gen_wavemaker()
         sys.exit(0)
     if "--only-noise" in sys.argv:
         gen_noise()
         sys.exit(0)
-    if "--only-solvers" in sys.argv:   # the LAPACK-dependent fixtures (needs no /root/reference)
+    if "--only-solvers" in sys.argv:   # the LAPACK-dependent fixtures
         gen_solvers()
         gen_lapack_split()
         sys.exit(0)

@@ -1,11 +1,46 @@
 """Shared test helpers: build matched product/oracle problems from the same synthetic inputs."""
+import atexit
 import ctypes
+import glob
+import lzma
+import os
+import tempfile
 
 import numpy as np
 
 import oracle as orc
 from nekstab_next_amd import synthetic as syn
 from nekstab_next_amd.layout import NekLayout
+
+
+REFERENCE_FLD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_fld")
+_unpacked = None
+
+
+def _packed_name(rel: str) -> str:
+    return rel.replace("/", "__")
+
+
+def reference_file(rel: str) -> str:
+    """Path of the reference's base-flow field file ``rel`` (``examples/.../BF_*.f00001``), byte for
+    byte: the files are committed under ``tests/golden/reference_fld/`` as xz pieces
+    ``<rel with / as __>.<k>.xz`` (``tests/golden/make_golden.py --pack-reference`` wrote them) and
+    unpacked once per process into a temporary directory."""
+    global _unpacked
+    if _unpacked is None:
+        _unpacked = tempfile.TemporaryDirectory(prefix="nkv_reference_fld_")
+        atexit.register(_unpacked.cleanup)
+    out = os.path.join(_unpacked.name, _packed_name(rel))
+    if not os.path.exists(out):
+        parts = sorted(glob.glob(os.path.join(REFERENCE_FLD_DIR, glob.escape(_packed_name(rel)) + ".*.xz")),
+                       key=lambda p: int(p.split(".")[-2]))
+        if not parts:
+            raise FileNotFoundError(f"no packed reference file for {rel} in {REFERENCE_FLD_DIR}")
+        with open(out, "wb") as fh:
+            for p in parts:
+                with lzma.open(p) as src:
+                    fh.write(src.read())
+    return out
 
 
 def olayout(lay: NekLayout, time_in_dot=False):

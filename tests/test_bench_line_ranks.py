@@ -23,7 +23,7 @@ def _port(k: int) -> str:
 def _line(world: int, port_k: int) -> dict:
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MASTER_PORT=_port(port_k), OMP_NUM_THREADS="2")
-    p = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--dry-line", "--E", "64", "--m", "8",
+    p = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--dry-line", "--full", "--E", "64", "--m", "8",
                         "--cpu-E", "8", "--cpu-E-1core", "8", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -119,7 +119,7 @@ def test_driver_launcher_two_ranks_one_line():
     env.update(OMP_NUM_THREADS="2", NKV_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", _port(9), BENCH, "--gpus", "2", "--dry-line",
-                        "--E", "64", "--cpu-E", "8", "--cpu-E-1core", "8", "--steps", "1", "--warmup", "0"],
+                        "--full", "--E", "64", "--cpu-E", "8", "--cpu-E-1core", "8", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -4,18 +4,16 @@ import os
 import numpy as np
 import pytest
 
+from helpers import reference_file
 from nekstab_next_amd import checkpoint as ck
 from nekstab_next_amd import fld
 from nekstab_next_amd import synthetic as syn
 from nekstab_next_amd.layout import NekLayout, cylinder_layout
 
-BF = "/root/reference/examples/cylinder/BF_1cyl0.f00001"
-
-
-@pytest.mark.skipif(not os.path.exists(BF), reason="reference data file not present (GPU box)")
 def test_reference_base_flow_roundtrip(tmp_path):
     """The cylinder base flow shipped with the reference (#std 8 6 6 1 1996 ... XUP) reads into the
     cylinder layout and writes back byte-compatible field data."""
+    BF = reference_file("examples/cylinder/BF_1cyl0.f00001")
     f = fld.read_fld(BF)
     assert (f.nx, f.ny, f.nz, f.nelgt, f.rdcode) == (6, 6, 1, 1996, "XUP")
     assert sorted(f.emap.tolist()) == list(range(1, 1997))

@@ -49,8 +49,8 @@ def _one_byte_model(d, check_peak=False):
 def test_bench_full_size_no_gbs_field_above_peak(gpu):
     """The driver's workload (config 3, N=100,014,464, m=128), one timed step: no GB/s field of the
     line exceeds the 8 TB/s peak, the roofline fraction is the dominant kernel's."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu",
-                        "--no-ks"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full",
+                        "--no-cpu", "--no-ks"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -63,7 +63,7 @@ def test_bench_full_size_no_gbs_field_above_peak(gpu):
 
 def test_bench_json_contract(gpu):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--E", "2000", "--steps", "2", "--warmup", "1",
-                        "--cpu-E", "64", "--cpu-E-1core", "8"],
+                        "--full", "--cpu-E", "64", "--cpu-E-1core", "8"],
                        capture_output=True, text=True, timeout=240,
                        cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -98,6 +98,51 @@ def test_bench_json_contract(gpu):
     assert d["gram_schmidt"]["gs_ms_per_factorisation"] <= d["ms_per_step"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(gpu, tmp_path):
+    """Without ``--full`` the line keeps its headline fields and the legs beside them are null;
+    ``--dump-outputs`` writes the last timed step's outputs as float64 arrays, consistent with the
+    line and with one another (H's Ritz values are the dumped ones; sampled basis rows are W-orthonormal
+    only over the whole vector, so the sample is checked for shape, finiteness and its seeded rows)."""
+    import numpy as np
+
+    m = 48
+    outs = []
+    for k in range(2):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--E", "400", "--m", str(m),
+                            "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / f"o{k}")],
+                           capture_output=True, text=True, timeout=240, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and d["ms_per_step"] > 0
+        assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 0
+        assert d["roofline"]["frac"] > 0
+        for key in ("restart", "krylov_schur_leg", "krylov_schur_restart_leg", "cpu_baseline", "cpu_baseline_1core",
+                    "cpu_optimised"):
+            assert d[key] is None, key
+        arrs = {n[:-4]: np.load(tmp_path / f"o{k}" / n) for n in sorted(os.listdir(tmp_path / f"o{k}"))}
+        assert set(arrs) == {"ritz_values", "ritz_residuals", "hessenberg", "basis_sample", "basis_sample_rows"}
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        assert arrs["ritz_values"].shape == (m, 2) and arrs["ritz_residuals"].shape == (m,)
+        assert arrs["hessenberg"].shape == (m + 1, m)
+        assert arrs["basis_sample"].shape == (m + 1, arrs["basis_sample_rows"].size)
+        top8 = arrs["ritz_values"][:8]
+        np.testing.assert_allclose(top8, np.array(d["ritz_top8"]), rtol=0, atol=0)
+        ev = np.linalg.eigvals(arrs["hessenberg"][:m])
+        got = arrs["ritz_values"][:, 0] + 1j * arrs["ritz_values"][:, 1]
+        # every dumped Ritz value is an eigenvalue of the dumped H (two LAPACK calls on one matrix)
+        assert max(np.min(np.abs(ev - v)) for v in got) <= 1e-10 * np.max(np.abs(ev))
+        assert np.max(np.abs(arrs["basis_sample"])) > 0
+        outs.append(arrs)
+    # same arguments, same inputs: the sampled rows are the same, and so is the first basis vector
+    # (the hashed seed over its norm: one reduction of N terms and a division away from the input)
+    np.testing.assert_array_equal(outs[0]["basis_sample_rows"], outs[1]["basis_sample_rows"])
+    q0 = outs[0]["basis_sample"][0]
+    assert np.max(np.abs(q0 - outs[1]["basis_sample"][0])) <= 1e-13 * np.max(np.abs(q0))
+
+
 def test_bench_plain_command_two_gloo_ranks_one_gpu(gpu):
     """``python bench.py --gpus 2`` (no torchrun) spawns two ranks; with NKV_BACKEND=gloo both share
     the one GPU of this box.  One JSON line with n_gpus 2, and the same Ritz values as one rank."""
@@ -130,7 +175,7 @@ def test_bench_two_ranks_with_restart_and_krylov_schur_legs(gpu):
     (restart count, mstart and converged-count histories), with the same converged values."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["NKV_BACKEND"] = "gloo"
-    common = ["--E", "400", "--m", "48", "--steps", "1", "--warmup", "1", "--no-cpu"]
+    common = ["--E", "400", "--m", "48", "--steps", "1", "--warmup", "1", "--full", "--no-cpu"]
     outs = {}
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *common],

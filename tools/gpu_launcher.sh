@@ -8,7 +8,7 @@ TAG=${1:-launch}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout -k 10 300 python3 bench.py --steps 2 --warmup 1 --no-cpu --no-restart --no-ks > $O/b1.json 2> $O/b1.err || { echo b1 failed; tail $O/b1.err; exit 1; }
-NKV_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu > $O/b2.json 2> $O/b2.err || { echo b2 failed; tail $O/b2.err; exit 1; }
+NKV_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu > $O/b2.json 2> $O/b2.err || { echo b2 failed; tail $O/b2.err; exit 1; }
 timeout -k 10 120 python3 bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu > $O/b2nccl.json 2> $O/b2nccl.err; rc=$?
 echo "rccl 2 ranks on 1 GPU: rc=$rc"; tail -2 $O/b2nccl.err
 [ $rc -eq 2 ] || exit 1

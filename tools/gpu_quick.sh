@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU suite + one default bench line (no profiler).  usage (on the box): bash tools/gpu_quick.sh TAG [bench args]
+# GPU suite + one default bench line with every leg (--full; no profiler).  usage (on the box): bash tools/gpu_quick.sh TAG [bench args]
 set -o pipefail
 TAG=${1:-run}; shift
 R=$GRAFT_REPO_ROOT
@@ -8,5 +8,5 @@ mkdir -p $O
 cd $R
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { echo "pytest failed"; tail -40 $O/pytest_gpu.log; exit 1; }
 tail -3 $O/pytest_gpu.log
-timeout -k 10 600 python3 bench.py "$@" > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json

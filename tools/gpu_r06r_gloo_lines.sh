@@ -6,8 +6,8 @@ O=gpurun_out/r06r
 mkdir -p $O
 (while sleep 50; do date >> $O/heartbeat.txt; done) &
 HB=$!
-NKV_BACKEND=gloo timeout -k 10 700 python3 -u bench.py --gpus 8 --steps 2 --warmup 1 > $O/bench_8rank_gloo.json 2> $O/bench_8rank_gloo.err && \
-NKV_BACKEND=gloo timeout -k 10 400 python3 -u bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err
+NKV_BACKEND=gloo timeout -k 10 700 python3 -u bench.py --gpus 8 --steps 2 --warmup 1 --full > $O/bench_8rank_gloo.json 2> $O/bench_8rank_gloo.err && \
+NKV_BACKEND=gloo timeout -k 10 400 python3 -u bench.py --gpus 2 --steps 2 --warmup 1 --full > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err
 RC=$?
 kill $HB
 exit $RC

@@ -6,7 +6,7 @@ mkdir -p $O
 (while sleep 50; do date >> $O/heartbeat.txt; done) &
 HB=$!
 NKV_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_torchrun_2rank.json 2> $O/bench_torchrun_2rank.err
+  --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --full > $O/bench_torchrun_2rank.json 2> $O/bench_torchrun_2rank.err
 RC=$?
 kill $HB
 exit $RC
