@@ -83,6 +83,8 @@ extern "C" {
 #define NKV_CHECK_BREAKDOWN 0x80u /* one-call factorisations: check the new H columns on return      */
 #define NKV_MGS_ICWY 0x100u /* arnoldi_factorization: both MGS passes in inverse compact WY form (3 reads) */
 #define NKV_MGS_LAGGED 0x200u /* arnoldi_factorization: MGS2 coefficients, second pass lagged (2 reads) */
+#define NKV_SFD_MONITOR 0x400u /* sfd_step: no filter, no forcing (continuation mode): residual and v_old only */
+#define NKV_TDF_STORE 0x800u  /* tdf_step: store v in the slot only (the first period), no forcing        */
 
 typedef struct nkv_layout {
     int64_t n_v;  /* live points per weighted field on this rank (lx1*ly1*lz1*nelv)  */
@@ -454,6 +456,42 @@ double nkv_givens_column(int k, double* h, double* cs, double* sn, double* g);
  * drivers.hip; nkv_arnoldi_factorization with NKV_MGS_LAGGED runs the whole sequence. */
 int nkv_lagged_coef(int c, int stage, const double* hv, double* G, int64_t ldg, double* H, int64_t ldh,
                     double* coef);
+
+/* ---- fixed-point forcing (core/fixedp.f90; dispatched at core/main.f90:156-176) ------------------
+ * Both entries are one streaming pass over state vectors in the layout above; `fc` is the forcing
+ * (fcx, fcy, [fcz], fct.., fcp) as one such vector.  res2_dev[0] receives the LOCAL partial of
+ * sum w r r over the first n_vel (2 or 3, <= n_wf: the velocities) weighted fields, reduced in a
+ * fixed order through the workspace partials (a NaN raises the workspace flag); the caller
+ * all-reduces it and forms normvc's l2 = sqrt(res2 / volume) (normvc is Nek5000's, :72, :187).  The
+ * time slot of every vector is left alone (the reference never sets oldQ%time and friends).  An empty
+ * shard (n_v = 0) writes res2 = 0 and nothing else.
+ *
+ * nkv_sfd_step: SFD for istep >= 1 (fixedp.f90:157-189), per stored row, in this order, uncontracted:
+ *     d     = v_old - qbar                         k_sub3(qa, oldV, oldQ)            :160
+ *     m     = ((adt d) + (bdt qa)) + (cdt qb)      tempM                             :161-169
+ *     qbar' = qbar + cutoff_dt m                   k_cmult(tempM, cutoff*dt), k_add2 :170-171
+ *     fc'   = fc + gain (v_old - qbar')            the lagged flow, as the reference :174-176
+ *     r     = v_old - v;  res2 += w r r            nopsub2, normvc (velocities only) :186-187
+ *     v_old'= v                                    nopcopy                           :189
+ *   qa, qb: the previous two d's; qd receives d.  The host rotates the three buffers (qd holds the
+ *   reference's qc on entry; after the call qb <- qa, qa <- qd, qd <- the old qb) instead of the
+ *   k_copy(qc, qb), k_copy(qb, qa) of :158-159.  (adt, bdt, cdt): Nek5000's setab3 (:157).
+ *   v_old, qbar, fc are updated in place; qd may alias none of the other vectors.
+ *   NKV_SFD_MONITOR: the continuation branch (uparam(5) <= 0, :178-183): only r, res2 and v_old';
+ *   qbar, qa, qb, qd, fc are not read (may be NULL).
+ * nkv_tdf_step: one TDF step on one slot of the orbit ring (fixedp.f90:71-96; `slot` holds the flow
+ *   one period ago, the reference's uor/vor/wor/tor(:,1), so its O(norbit N) history shift :77-89
+ *   becomes one slot read and written):
+ *     first n_vel fields:  r = v - slot;  res2 += w r r;  fc += gain r;  slot <- v   :71-75, :90
+ *     scalar fields:       slot <- v                                                  :91-96
+ *   The pressure segment of slot and fc is not touched.  NKV_TDF_STORE (istep <= norbit, :58-67):
+ *   slot <- v on every weighted field, no forcing (fc may be NULL), res2 = 0. */
+int nkv_sfd_step(const nkv_layout* L, const double* w, const double* v, double* v_old, double* qbar,
+                 const double* qa, const double* qb, double* qd, double* fc, double adt, double bdt, double cdt,
+                 double cutoff_dt, double gain, int n_vel, double* res2_dev, void* ws, unsigned flags,
+                 void* stream);
+int nkv_tdf_step(const nkv_layout* L, const double* w, const double* v, double* slot, double* fc, double gain,
+                 int n_vel, double* res2_dev, void* ws, unsigned flags, void* stream);
 
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live

@@ -15,7 +15,10 @@ def __getattr__(name):
     import importlib
 
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
-                "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "_lib"):
+                "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
+                "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
+    if name in ("SFD", "TDF"):   # the fixed-point forcing classes (fixedp.py)
+        return getattr(importlib.import_module(".fixedp", __name__), name)
     raise AttributeError(name)

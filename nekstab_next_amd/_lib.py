@@ -32,6 +32,8 @@ NKV_MGS2 = 0x40
 NKV_MGS_ICWY = 0x100
 NKV_MGS_LAGGED = 0x200
 NKV_CHECK_BREAKDOWN = 0x80
+NKV_SFD_MONITOR = 0x400
+NKV_TDF_STORE = 0x800
 
 
 class NkvError(RuntimeError):
@@ -119,6 +121,9 @@ _SIGNATURES = {
     "nkv_givens_column": (c_double, [c_int, _P, _P, _P, _P]),
     "nkv_lagged_coef": (c_int, [c_int, c_int, _P, _P, c_int64, _P, c_int64, _P]),
     "nkv_gkl_coef": (c_int, [c_int, c_int, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int64, _P, _P, _P]),
+    "nkv_sfd_step": (c_int, [_L, _P, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_double, c_double,
+                             c_int, _P, _P, c_uint, _P]),
+    "nkv_tdf_step": (c_int, [_L, _P, _P, _P, _P, c_double, c_int, _P, _P, c_uint, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

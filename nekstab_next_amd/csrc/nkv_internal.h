@@ -18,6 +18,7 @@
 //   drivers.hip       one-call factorisations (DCGS2, CGS2/MGS2, MGS2-ICWY), GMRES cycle, Givens column
 //   operators.hip     synthetic operators and the hashed test vectors
 //   sensitivity.hip   seed noise (mth_rand), symmetric seed, wave-maker, gradm1, base-flow sensitivity
+//   fixedp.hip        fixed-point forcing: fused SFD step, TDF step on a ring slot (residual from the same pass)
 #pragma once
 
 #include <hip/hip_runtime.h>
