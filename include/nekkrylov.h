@@ -493,6 +493,50 @@ int nkv_sfd_step(const nkv_layout* L, const double* w, const double* v, double* 
 int nkv_tdf_step(const nkv_layout* L, const double* w, const double* v, double* slot, double* fc, double gain,
                  int n_vel, double* res2_dev, void* ws, unsigned flags, void* stream);
 
+/* ---- eigenmode kinetic-energy budget (stability_energy_budget, postproc.f90:649-872; uparam(1) = 4.1) ----
+ * lx1, ldim, D, xm, ym, zm: as nkv_gradm1 (ldim 2 or 3, lx1 <= 10, lx1^ldim points per element divide
+ * n_v, zm exactly when ldim = 3).  Every field is n_v points in Nek point order; strides are in doubles
+ * and at least n_v.  All arithmetic is f64 without contraction in the reference's operand order.  Each
+ * entry is one grid-stride kernel (the two reducing ones followed by the fixed-order second stage of
+ * nkv_dot), no host synchronisation, no atomics, 64-bit point offsets, element-local.  A bad argument
+ * returns NKV_EINVAL with a message naming it.
+ *
+ * nkv_pke_production: compute_production for all base components (postproc.f90:801-836) and the glsc2
+ *   of its terms (:728-730) in one tiled pass.  Base component c (ubase + c*b_stride) is differentiated in
+ *   LDS with nkv_gradm1's arithmetic (no dsavg, :814, :821, :828), then for direction d
+ *     P[c][d] = -0.5 (re_c re_d + im_d im_c) dbase_c/dx_d     (diagonal: re_c**2 + im_c**2; :816-832)
+ *   with re_c = dRe + c*m_stride, im_c = dIm + c*m_stride, written to prod + (c*ldim + d)*p_stride (the
+ *   reference's energy_budget(:, 3c+d+1); prod may be NULL: integrals only), and
+ *     integrals_dev[c*ldim + d] = sum_p bm1[p] P[c][d][p]      (bm1: the mass matrix, n_v weights)
+ *   as this rank's LOCAL partial sum, reduced in a fixed order through the workspace partials (run-to-run
+ *   deterministic; a NaN raises the workspace flag).  Workspace: ldim^2 <= 9 partials per workgroup, i.e.
+ *   nkv_workspace_bytes(L, max_cols >= 4); the grid is capped at the NKV_MAXB workgroups that size
+ *   holds.  In 2-D the terms with a z factor are absent (the reference reads never-set arrays there).
+ *   An empty shard (n_v = 0) writes ldim^2 zeros and reads nothing else.
+ * nkv_divm1: the divergence that closes compute_laplacian (postproc.f90:853-872: Lap a = d2x + d2y + d2z,
+ *   :865-869) for nvec vector fields at once: component d of vector v at g + (v*ldim + d)*g_stride,
+ *     div_v = (dg_vx/dx + dg_vy/dy) [+ dg_vz/dz]   ->   div + v*d_stride,
+ *   every partial derivative exactly what nkv_gradm1 writes for that field and direction (the reference
+ *   takes a full gradient of each first derivative and keeps one of its three outputs, :865-867).  The
+ *   geometric factors are formed once for all nvec.  An empty shard touches nothing.
+ * nkv_pke_dissipation: compute_dissipation's pointwise part (postproc.f90:784-796) and its glsc2 (:729),
+ *   streaming (16-byte loads when every base and stride allows).  lap: 2*ncomp segments of l_stride, the
+ *   Laplacians of the Re components then of the Im components.  Per point
+ *     dummy_c = re_c lap_re_c + im_c lap_im_c;   diss = ((0 + dummy_x) + dummy_y) [+ dummy_z]   (:785-794)
+ *     diss = (0.5 diss) nu,  nu = param(2)/param(1)                                              (:796)
+ *   written to diss (n_v doubles; may be NULL), and integral_dev[0] = sum_p bm1[p] diss[p], local and
+ *   reduced as above (one partial per workgroup).  An empty shard writes 0. */
+int nkv_pke_production(const nkv_layout* L, int lx1, int ldim, const double* D, const double* xm, const double* ym,
+                       const double* zm, const double* ubase, int64_t b_stride, const double* dRe, const double* dIm,
+                       int64_t m_stride, const double* bm1, double* prod, int64_t p_stride, double* integrals_dev,
+                       void* ws, void* stream);
+int nkv_divm1(const nkv_layout* L, int lx1, int ldim, const double* D, const double* xm, const double* ym,
+              const double* zm, const double* g, int nvec, int64_t g_stride, double* div, int64_t d_stride,
+              void* stream);
+int nkv_pke_dissipation(const nkv_layout* L, const double* dRe, const double* dIm, int64_t m_stride,
+                        const double* lap, int64_t l_stride, int ncomp, double nu, const double* bm1, double* diss,
+                        double* integral_dev, void* ws, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

@@ -124,6 +124,10 @@ _SIGNATURES = {
     "nkv_sfd_step": (c_int, [_L, _P, _P, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_double, c_double,
                              c_int, _P, _P, c_uint, _P]),
     "nkv_tdf_step": (c_int, [_L, _P, _P, _P, _P, c_double, c_int, _P, _P, c_uint, _P]),
+    "nkv_pke_production": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64,
+                                   _P, _P, _P]),
+    "nkv_divm1": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int64, _P, c_int64, _P]),
+    "nkv_pke_dissipation": (c_int, [_L, _P, _P, c_int64, _P, c_int64, c_int, c_double, _P, _P, _P, _P, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

@@ -19,6 +19,7 @@
 //   operators.hip     synthetic operators and the hashed test vectors
 //   sensitivity.hip   seed noise (mth_rand), symmetric seed, wave-maker, gradm1, base-flow sensitivity
 //   fixedp.hip        fixed-point forcing: fused SFD step, TDF step on a ring slot (residual from the same pass)
+//   postproc.hip      eigenmode kinetic-energy budget: fused production terms + integrals, divergence, dissipation
 #pragma once
 
 #include <hip/hip_runtime.h>
