@@ -537,6 +537,67 @@ int nkv_pke_dissipation(const nkv_layout* L, const double* dRe, const double* dI
                         const double* lap, int64_t l_stride, int ncomp, double nu, const double* bm1, double* diss,
                         double* integral_dev, void* ws, void* stream);
 
+/* ---- flow diagnostics: vortex criteria, filter_s0, energy / enstrophy sums -------------------------
+ * (vortex_core and its criteria, postproc.f90:2-522; outpost_vort / nekStab_outpost, utils.f90:420-444,
+ * 489-536; nekStab_energy / nekStab_enstrophy, utils.f90:647-716.)
+ * lx1, ldim, D, xm, ym, zm and the field conventions: as for the energy budget above.  All arithmetic is
+ * f64 without contraction in the reference's operand order; tiled element kernels (the tile of nkv_gradm1),
+ * no host synchronisation, no atomics, 64-bit point offsets, element-local.  A bad argument returns
+ * NKV_EINVAL with a message naming it; an empty shard (n_v = 0) returns NKV_OK and reads no pointer.
+ *
+ * Criterion codes; a mask holds bit (1u << code) per criterion.  Output slots are numbered in ascending
+ * code order over the selected criteria; vorticity takes three slots in 3-D (x, y, z) and one in 2-D. */
+enum nkv_vortex_criterion {
+    NKV_VC_VORTICITY = 0,  /* curl of the velocity (comp_vort3 before its averaging): (g32-g23, g13-g31, g21-g12) */
+    NKV_VC_LAMBDA2 = 1,    /* middle eigenvalue of S^2 + Omega^2 (Nek5000's lambda2), 3-D only, never filtered */
+    NKV_VC_Q = 2,          /* compute_q, :148-175 / compute_secondInv :371-400 (2-D form as written, :395-396) */
+    NKV_VC_DELTA = 3,      /* compute_delta, :177-210 */
+    NKV_VC_SWIRLING = 4,   /* compute_swirling, :212-305: lambda_ci, filtered, then squared (:298-302) */
+    NKV_VC_OMEGA = 5,      /* compute_omega_jc, :31-79 */
+    NKV_VC_SYMMETRIC = 6,  /* compute_symmetricVec, :106-125 / compute_symmetric :327-344 */
+    NKV_VC_ASSYMETRIC = 7, /* compute_assymetricVec, :127-146 / compute_antisymmetric :307-325 (its '+' kept) */
+    NKV_VC_LAMBDA_CI = 8,  /* the swirling strength lambda_ci itself: swirling before its square (filtered alike) */
+    NKV_VC_COUNT = 9
+};
+/* nkv_vortex_criteria: one tiled pass over whole elements.  The ldim velocity components (u + c*u_stride)
+ *   and the coordinates are staged in LDS, the tensor g[i][j] = du_i/dx_j is formed per point with every
+ *   entry exactly what nkv_gradm1 writes for that component and direction, and every criterion in `mask`
+ *   is evaluated from it and stored once at out + slot*o_stride.  A criterion that is also in
+ *   `filter_mask` goes through filter_s0 (below) in LDS before its store when F (lx1 x lx1, row-major,
+ *   device) is given; F = NULL, or a criterion outside filter_mask, stores the raw value.  vorticity and
+ *   lambda2 are never filtered (vortex_core calls lambda2 without filter_s0, :8-9).  swirling is squared
+ *   after the filter (:298-302), or directly when unfiltered.  grad (may be NULL) receives the ldim^2
+ *   tensor entries at grad + (i*ldim + j)*g_stride.  mask = 0 is allowed with grad (out is then unused).
+ *   With I, II, III the invariants of g (:346-435) and P1 = -I, Q1 = II, R1 = -III:
+ *     q = II;   delta = (R/2)^2 + (Q/3)^3,  Q = Q1 - P1^2/3,  R = R1 + 2 P1^3/27 - P1 Q1/3;
+ *     swirling: cubicLambdaCi(P1, Q1, R1) (:437-474) in 3-D, quadLambdaCi(P1, R1) (:476-500) in 2-D;
+ *     omega = b / (a + b + 1e-5),  a = (sum ss_ij^2)^2,  b = (sum oo_ij^2)^2  (sums taken directly, i fastest);
+ *     assymetric = ((g12+g21)^2 + (g13+g31)^2 + (g23+g32)^2)/4,  symmetric = that + (g11^2+g22^2+g33^2)/2;
+ *     lambda2: the middle eigenvalue of A = S^2 + Omega^2 after five cyclic Jacobi sweeps over (0,1), (0,2),
+ *       (1,2) (+ - * / sqrt only; the trigonometric closed form loses half the digits at a double
+ *       eigenvalue, i.e. in a solid-body rotation).
+ *   lambda2 at ldim = 2 and F with lx1 < 3 are refused.  LDS: (2 lx1^2 + 2 ldim nt) doubles, 49,600 bytes at
+ *   lx1 = 10 in 3-D (the coordinate tiles double as the filter's scratch).
+ * nkv_filter_s0: Nek5000's filter_s0 / filterq with the matrix F on nfld fields (field f at v + f*v_stride,
+ *   result at out + f*o_stride; out may equal v with o_stride = v_stride: in place): along r, then s, then t
+ *     v'(i,j,k) = sum_m F[i][m] v(m,j,k)     (m ascending, products not contracted).
+ *   The same device routine as the fused filter, so a fused filtered output equals the raw output followed
+ *   by this entry bit for bit.  3 <= lx1 <= 10.
+ * nkv_energy_components: sums_dev[c] = sum_p f_c[p] w[p] f_c[p] for the ncomp <= 3 segments f + c*f_stride
+ *   (glsc3(px, bm1s, px), utils.f90:671-673, 708-710; entries ncomp..2 are 0) and, when t and y are given
+ *   (both or neither), sums_dev[3] = sum_p t[p] w[p] y[p] (pot, :674; else 0): four doubles, this rank's
+ *   LOCAL partial sums reduced in a fixed order through the workspace partials (four per workgroup,
+ *   nkv_workspace_bytes(L, max_cols >= 4)); a NaN raises the workspace flag.  16-byte loads when every
+ *   base and stride allows.  An empty shard writes four zeros. */
+int nkv_vortex_criteria(const nkv_layout* L, int lx1, int ldim, const double* D, const double* F, const double* xm,
+                        const double* ym, const double* zm, const double* u, int64_t u_stride, unsigned mask,
+                        unsigned filter_mask, double* out, int64_t o_stride, double* grad, int64_t g_stride,
+                        void* stream);
+int nkv_filter_s0(const nkv_layout* L, int lx1, int ldim, const double* F, const double* v, int64_t v_stride,
+                  int nfld, double* out, int64_t o_stride, void* stream);
+int nkv_energy_components(const nkv_layout* L, const double* w, const double* f, int64_t f_stride, int ncomp,
+                          const double* t, const double* y, double* sums_dev, void* ws, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

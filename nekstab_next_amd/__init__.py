@@ -16,7 +16,7 @@ def __getattr__(name):
 
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
                 "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
-                "postproc", "_lib"):
+                "postproc", "vortex", "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
     if name in ("SFD", "TDF"):   # the fixed-point forcing classes (fixedp.py)

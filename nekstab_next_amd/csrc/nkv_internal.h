@@ -20,6 +20,8 @@
 //   sensitivity.hip   seed noise (mth_rand), symmetric seed, wave-maker, gradm1, base-flow sensitivity
 //   fixedp.hip        fixed-point forcing: fused SFD step, TDF step on a ring slot (residual from the same pass)
 //   postproc.hip      eigenmode kinetic-energy budget: fused production terms + integrals, divergence, dissipation
+//   vortex.hip        flow diagnostics: fused vortex criteria (+ filter_s0 in LDS), standalone filter_s0,
+//                     energy / enstrophy component sums
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -304,5 +306,147 @@ inline double* partials_of(void* ws) {
 inline bool use_large_tiles(const nkv_layout* L) {
     return rows_of(L) / (kThreads * NKV_PAIRS * 2) >= NKV_SMALL_TILES;
 }
+
+// ------------------------------------------------------------------------------------------
+// The element tile of k_gradm1 (sensitivity.hip), shared by the tiled element kernels of postproc.hip
+// and vortex.hip: whole elements per workgroup, whole waves, one point per thread.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+constexpr int tile_pts() { return LDIM == 3 ? NX * NX * NX : NX * NX; }
+template <int LDIM, int NX>
+constexpr int tile_threads() {
+    return tile_pts<LDIM, NX>() >= 256 ? (tile_pts<LDIM, NX>() + 63) / 64 * 64 : 256;
+}
+inline int tile_epb(int pts) { return pts >= 256 ? 1 : 256 / pts; }
+constexpr int kMaxWaves = 16;   // 1024 threads (lx1 = 10 in 3-D: 1000 points)
+
+// This thread's point of the tile: its element, its three lines and its rows of D (LDS).
+template <int LDIM, int NX>
+struct TilePoint {
+    int ri, si, ti;                 // lines along r, s, t through the point
+    const double *Di, *Dj, *Dk;
+    __device__ __forceinline__ TilePoint(const double* D, int tid, int nt) {
+        constexpr int pts = tile_pts<LDIM, NX>();
+        const int le = tid / pts, r = tid - le * pts;
+        const int i = r % NX, j = (r / NX) % NX, k = LDIM == 3 ? r / (NX * NX) : 0;
+        const int base = (tid < nt ? le : 0) * pts;   // lanes past the last whole element read element 0
+        ri = base + j * NX + k * NX * NX;
+        si = base + i + k * NX * NX;
+        ti = base + i + j * NX;
+        Di = D + i * NX;
+        Dj = D + j * NX;
+        Dk = D + k * NX;
+    }
+};
+
+// glmapm1 / xyzrst's geometric factors of one point from the staged coordinates: the arithmetic of
+// k_gradm1, operation for operation (mxm line sums with m ascending, addcol4 / subcol4 Jacobian,
+// ascol5 cofactors).  g[direction][reference coordinate r, s, t].
+template <int LDIM, int NX>
+__device__ __forceinline__ void geometric_factors(const TilePoint<LDIM, NX>& q, const double* X, const double* Y,
+                                                  const double* Z, double (&g)[3][3], double& jacmi) {
+#pragma clang fp contract(off)
+    constexpr int sj = NX, sk = NX * NX;
+    const double *Di = q.Di, *Dj = q.Dj, *Dk = q.Dk;
+    const int ri = q.ri, si = q.si, ti = q.ti;
+    double xr = Di[0] * X[ri], yr = Di[0] * Y[ri];
+    double xs = X[si] * Dj[0], ys = Y[si] * Dj[0];
+#pragma unroll 2
+    for (int m = 1; m < NX; ++m) {
+        xr = xr + Di[m] * X[ri + m];
+        yr = yr + Di[m] * Y[ri + m];
+        xs = xs + X[si + m * sj] * Dj[m];
+        ys = ys + Y[si + m * sj] * Dj[m];
+    }
+    if constexpr (LDIM == 2) {
+        double jac = 0.0;
+        jac = jac + xr * ys;
+        jac = jac - xs * yr;
+        g[0][0] = ys;
+        g[1][0] = -xs;
+        g[0][1] = -yr;
+        g[1][1] = xr;
+        jacmi = 1.0 / jac;
+    } else {
+        double zr = Di[0] * Z[ri], zs = Z[si] * Dj[0];
+        double xt = X[ti] * Dk[0], yt = Y[ti] * Dk[0], zt = Z[ti] * Dk[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) {
+            zr = zr + Di[m] * Z[ri + m];
+            zs = zs + Z[si + m * sj] * Dj[m];
+            xt = xt + X[ti + m * sk] * Dk[m];
+            yt = yt + Y[ti + m * sk] * Dk[m];
+            zt = zt + Z[ti + m * sk] * Dk[m];
+        }
+        double jac = 0.0;
+        jac = jac + xr * ys * zt;
+        jac = jac + xt * yr * zs;
+        jac = jac + xs * yt * zr;
+        jac = jac - xr * yt * zs;
+        jac = jac - xs * yr * zt;
+        jac = jac - xt * ys * zr;
+        g[0][0] = ys * zt - yt * zs;   // rx
+        g[1][0] = xt * zs - xs * zt;   // ry
+        g[2][0] = xs * yt - xt * ys;   // rz
+        g[0][1] = yt * zr - yr * zt;   // sx
+        g[1][1] = xr * zt - xt * zr;   // sy
+        g[2][1] = xt * yr - xr * yt;   // sz
+        g[0][2] = yr * zs - ys * zr;   // tx
+        g[1][2] = xs * zr - xr * zs;   // ty
+        g[2][2] = xr * ys - xs * yr;   // tz
+        jacmi = 1.0 / jac;
+    }
+}
+
+// ur, us, [ut] of one staged field at this point (k_gradm1's line sums).
+template <int LDIM, int NX>
+__device__ __forceinline__ void line_sums(const TilePoint<LDIM, NX>& q, const double* U, double& ur, double& us,
+                                          double& ut) {
+#pragma clang fp contract(off)
+    constexpr int sj = NX, sk = NX * NX;
+    ur = q.Di[0] * U[q.ri];
+    us = U[q.si] * q.Dj[0];
+    ut = 0.0;
+#pragma unroll 2
+    for (int m = 1; m < NX; ++m) {
+        ur = ur + q.Di[m] * U[q.ri + m];
+        us = us + U[q.si + m * sj] * q.Dj[m];
+    }
+    if constexpr (LDIM == 3) {
+        ut = U[q.ti] * q.Dk[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) ut = ut + U[q.ti + m * sk] * q.Dk[m];
+    }
+}
+
+// The derivative along direction d exactly as k_gradm1 stores it: jacmi * acc.
+template <int LDIM>
+__device__ __forceinline__ double physical_derivative(const double (&g)[3][3], double jacmi, int d, double ur,
+                                                      double us, double ut) {
+#pragma clang fp contract(off)
+    const double acc = LDIM == 3 ? ur * g[d][0] + us * g[d][1] + ut * g[d][2] : ur * g[d][0] + us * g[d][1];
+    return jacmi * acc;
+}
+
+// The argument checks the tiled element entries share with nkv_gradm1.
+inline int check_mesh_args(const char* who, const nkv_layout* L, int lx1, int ldim, const double* zm) {
+    if (ldim != 2 && ldim != 3) return fail(NKV_EINVAL, "%s: ldim=%d must be 2 or 3", who, ldim);
+    if (lx1 < 2 || lx1 > 10) return fail(NKV_EINVAL, "%s: lx1=%d outside 2..10", who, lx1);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    if (L->n_v % pts != 0)
+        return fail(NKV_EINVAL, "%s: %d points per element (lx1=%d) do not divide n_v=%lld", who, pts, lx1,
+                    (long long)L->n_v);
+    if ((ldim == 3) != (zm != nullptr)) return fail(NKV_EINVAL, "%s: zm must be given exactly in 3-D", who);
+    return NKV_OK;
+}
+
+inline int need(const void* p, const char* who, const char* what) {
+    if (!p) return fail(NKV_EINVAL, "%s: %s is NULL", who, what);
+    return NKV_OK;
+}
+
+// One switch case per supported lx1 (template parameter NX) of the tiled element kernels.
+#define NKV_PP_CASES(CALL) \
+    CALL(2) CALL(3) CALL(4) CALL(5) CALL(6) CALL(7) CALL(8) CALL(9) CALL(10)
 
 }  // namespace

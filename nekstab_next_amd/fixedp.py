@@ -152,16 +152,20 @@ class SFD:
     they are ``bm1``; with sponge-zeroed ``bm1s`` pass the full volume).  ``normvc`` is Nek5000's, not
     part of the reference tree: its l2 is sqrt(sum_c glsc3(u_c, bm1, u_c) / volvm1) over the
     velocities, which is what ``step`` returns with the context's weights.  ``residu``: a path for the
-    ``residu.dat`` records (rank 0).
+    ``residu.dat`` records (rank 0).  ``monitors``: callables ``m(v, istep, time)`` run at the end of
+    every step, e.g. ``vortex.EnergyMonitor`` / ``vortex.EnstrophyMonitor`` (the reference calls
+    ``nekStab_energy`` / ``nekStab_enstrophy`` from every step, main.f90:152-163); default none, and
+    then nothing changes.
 
     The time slots of the internal vectors are never touched (the reference's ``oldQ%time`` etc. are
     never set either).
     """
 
     def __init__(self, ctx: NekContext, uparam4: float, uparam5: float, dt: float, tol: float,
-                 volume: float | None = None, min_steps: int = 100, residu=None):
+                 volume: float | None = None, min_steps: int = 100, residu=None, monitors=()):
         _refuse_pair(ctx, "SFD")
         self.ctx = ctx
+        self.monitors = tuple(monitors)   # called as m(v, istep, time) after every step (main.f90:152-163)
         self.monitor = sfd_is_monitor(uparam5)
         self.cutoff, self.gain = sfd_coefficients(uparam4, uparam5)
         self.dt, self.tol, self.min_steps = float(dt), float(tol), int(min_steps)
@@ -217,6 +221,8 @@ class SFD:
         rate = (res - self.old_res) / self.dt
         self.old_res = res
         self._file.write(self.istep * self.dt if time is None else time, res, rate, self.tol)
+        for m in self.monitors:
+            m(v, self.istep, self.istep * self.dt if time is None else time)
         return res, rate, sfd_converged(self.istep, res, self.tol, self.min_steps)
 
     def close(self) -> None:
@@ -229,7 +235,7 @@ class TDF:
     ``period``: the orbit's period 1/uparam(5) (:20); ``dt_target``: the CFL time step (:22-23);
     norbit, ``dt`` (the caller must step with it) and the gain follow :func:`tdf_parameters`.  The
     orbit history is a :class:`Basis` of norbit slots used as a ring (:func:`tdf_slot`) instead of
-    the reference's shifted arrays.  ``volume`` and ``residu`` as for :class:`SFD`.
+    the reference's shifted arrays.  ``volume``, ``residu`` and ``monitors`` as for :class:`SFD`.
 
     The reference computes l2 only from step norbit + 2 on but its ``rate = l2 - residu0`` runs at
     norbit + 1 on an undefined l2 (:72: the ``if`` guards the ``call normvc`` alone); here the
@@ -237,9 +243,10 @@ class TDF:
     """
 
     def __init__(self, ctx: NekContext, period: float, dt_target: float, tol: float, volume: float | None = None,
-                 residu=None):
+                 residu=None, monitors=()):
         _refuse_pair(ctx, "TDF")
         self.ctx = ctx
+        self.monitors = tuple(monitors)   # called as m(v, istep, time) after every step (main.f90:152-163)
         self.period = float(period)
         self.norbit, self.dt, self.gain = tdf_parameters(period, dt_target)
         self.tol = float(tol)
@@ -263,6 +270,7 @@ class TDF:
         if self.istep <= self.norbit:
             ctx.call("nkv_tdf_step", w, v.ptr, slot, None, 0.0, self.n_vel, self._res2.data_ptr(), ws,
                      _lib.NKV_TDF_STORE, st)
+            self._monitor(v, time)
             return 0.0, 0.0, False
         ctx.call("nkv_tdf_step", w, v.ptr, slot, fc.ptr, self.gain, self.n_vel, self._res2.data_ptr(), ws, 0, st)
         ctx.comm.allreduce_(self._res2)
@@ -273,7 +281,12 @@ class TDF:
         rate = l2 - self.residu0
         self.residu0 = l2
         self._file.write(self.istep * self.dt if time is None else time, l2, rate)
+        self._monitor(v, time)
         return l2, rate, tdf_converged(l2, self.tol)
+
+    def _monitor(self, v: NekVector, time: float | None) -> None:
+        for m in self.monitors:
+            m(v, self.istep, self.istep * self.dt if time is None else time)
 
     def close(self) -> None:
         self._file.close()

@@ -308,7 +308,8 @@ def orthonormality_report(ctx: NekContext, Q: Basis, k: int) -> np.ndarray:
 
 def outpost_ks(ctx: NekContext, res: KrylovSchurResult, outdir: str, evop: str = "d", period: float = 1.0,
                maxmodes: int = 20, session: str = "nek", k: int | None = None,
-               orthonormality: bool = True, coords: dict | None = None, grad_tol: float = 1.1) -> dict:
+               orthonormality: bool = True, coords: dict | None = None, grad_tol: float = 1.1,
+               vorticity=None, vort_average="auto") -> dict:
     """The end of the in-tree ``krylov_schur`` (eigensolvers.f90:335-349) and ``outpost_ks``
     (:472-640): ``orthonormality.dat``; ``Spectre_H<evop>.dat`` (re, im, residual of every Ritz
     value, 3E15.7) and ``Spectre_NS<evop>.dat`` (log-transformed, divided by the sampling period
@@ -323,6 +324,10 @@ def outpost_ks(ctx: NekContext, res: KrylovSchurResult, outdir: str, evop: str =
     :class:`~.sensitivity.NormGrad`), and a mode with either above ``grad_tol`` (1.1) is skipped:
     not written, not in ``_conv.dat``, and the following modes take its output number (the
     reference's ``outp`` counter).  Without coords no mode is filtered (the mesh is the case's).
+
+    ``vorticity``: a :class:`~.vortex.VortexCore` of this context; when given, ``<evop>Rv`` holds
+    ``comp_vort3`` of every written real part next to its ``<evop>Re`` (``outpost_vort``, :610), averaged
+    with ``vort_average`` (as :meth:`~.vortex.VortexCore.comp_vort3`).  Default None: nothing changes.
     Returns the written mode indices, the skipped ones and every (Re, Im) gradient norm."""
     from . import fld
     from .checkpoint import log_transform
@@ -382,6 +387,11 @@ def outpost_ks(ctx: NekContext, res: KrylovSchurResult, outdir: str, evop: str =
             for vec, name in ((re_v, f"{evop}Re"), (im_v, f"{evop}Im")):
                 f = fld.fld_from_vector(lay, vec.to_packed(), time=float(num), istep=num)
                 write(fld.write_fld, os.path.join(outdir, fld.fld_name(name, session, lay.rank, num)), f)
+                if vorticity is not None and name.endswith("Re"):
+                    from .vortex import outpost_vort
+
+                    outpost_vort(ctx, vec, f"{evop}Rv", num, core=vorticity, outdir=outdir, session=session,
+                                 average=vort_average, time=float(num), istep=num, write=write)
             lt = log_transform(res.vals[i])
             conv_lines.append(f"{lt.real / period:15.7E}{lt.imag / period:15.7E}\n")
             written.append(i)
