@@ -85,6 +85,8 @@ extern "C" {
 #define NKV_MGS_LAGGED 0x200u /* arnoldi_factorization: MGS2 coefficients, second pass lagged (2 reads) */
 #define NKV_SFD_MONITOR 0x400u /* sfd_step: no filter, no forcing (continuation mode): residual and v_old only */
 #define NKV_TDF_STORE 0x800u  /* tdf_step: store v in the slot only (the first period), no forcing        */
+#define NKV_BF_IMAG 0x1000u   /* body_force: the imaginary branch of the harmonic term (omega_t < 0)          */
+#define NKV_BF_PERTURBATION 0x2000u /* body_force: perturbation mode (jp /= 0): ff - fn v, no fc on scalars  */
 
 typedef struct nkv_layout {
     int64_t n_v;  /* live points per weighted field on this rank (lx1*ly1*lz1*nelv)  */
@@ -492,6 +494,49 @@ int nkv_sfd_step(const nkv_layout* L, const double* w, const double* v, double* 
                  void* stream);
 int nkv_tdf_step(const nkv_layout* L, const double* w, const double* v, double* slot, double* fc, double gain,
                  int n_vel, double* res2_dev, void* ws, unsigned flags, void* stream);
+
+/* ---- body-force hooks (core/forcing.f90) ---------------------------------------------------------------
+ * Both entries are one streaming pass (16-byte accesses, chunks that never straddle a field, all loads of
+ * a chunk before its stores), f64 without contraction in the reference's operand order, no reduction and no
+ * host synchronisation.  An empty shard (n_v = 0) launches nothing.
+ *
+ * nkv_sponge_fn: spng_set + mth_stepf (forcing.f90:157-251) and the weight mask of activate_sponge (:101-104).
+ *   xm, ym, zm: this rank's GLL coordinates, n_v points each (device; only the active dimensions are read).
+ *   sections: 6 doubles per dimension on the HOST, (xxmin_c, xxmin, xxmax, xxmax_c, wl, wr) of :192-195 with the
+ *   section widths of :126-132; `active` holds bit d when dimension d has a sponge (wl > 0 or wr > 0, :186).
+ *   Per point, for the active dimensions in ascending order,
+ *     r = 1                          x <= xxmin_c          (constant)
+ *         mth_stepf((xxmin - x)/wl)  x <  xxmin            (fall)
+ *         0                          x <= xxmax
+ *         mth_stepf((x - xxmax)/wr)  x <  xxmax_c          (rise)
+ *         1                          otherwise             (constant)
+ *     fn = max(fn, r),   mth_stepf(a) = 0 (a <= 0.001), 1/(1 + exp(1/(a - 1) + 1/a)) (a <= 0.999), 1 otherwise.
+ *   fn: one field of sv doubles; its padding rows [n_v, sv) are written 0 (no coordinate is read there).
+ *   w (may be NULL): the dot weights, sv doubles; w[i] = 0 wherever fn[i] != 0, in the same pass.
+ *   xxmax <= xxmin in an active dimension is refused (the reference prints "Sponge too wide", :198-199).
+ * nkv_body_force: nekStab_forcing + nekStab_forcing_temp (forcing.f90:2-79) over the weighted fields of a
+ *   state vector ff.  Every term is optional: a NULL pointer's stream is not read.  Left to right,
+ *   first n_vel fields (:14-48):
+ *     x = ff0 (NULL: the userf zero, 0.0)
+ *     x = x + fc                                                              :14-16
+ *     f_re, f_im given, c = cos(omega_t), s = sin(omega_t):                   :19-33
+ *       x = (x + f_re c) - f_im s         NKV_BF_IMAG:  x = (x + f_re s) + f_im c
+ *     fn given:  x = x + (fn (ref - v)) st     NKV_BF_PERTURBATION:  x = x - fn v  (no strength factor)   :35-50
+ *   remaining weighted fields, the scalars (:64-75):
+ *     x = ff0 | 0.0;   x = x + fc unless NKV_BF_PERTURBATION (:64);
+ *     fn given:  x = x + fn (ref - t)          NKV_BF_PERTURBATION:  x = x - fn t   (no strength, no harmonic)
+ *   ff0, fc, f_re, f_im, ref, v: vectors in the layout above (ref: the spng_init snapshot, v: the current
+ *   flow or perturbation); fn: one field of sv doubles.  Only the n_v live rows of each weighted field of ff
+ *   are written: pressure, padding rows and the time slot are left alone.  ff may alias ff0 (accumulate in
+ *   place); any other aliasing of ff returns NKV_EINVAL.  n_vel: 2 or 3 and <= n_wf, as nkv_sfd_step.
+ *   Streams of n_v doubles: the fullest 3-D DNS case (fc, harmonic, sponge; ff0 NULL) reads 5 ldim + 1 (fn is
+ *   read once per chunk of rows for all fields) and writes ldim; the sponge term alone in perturbation mode
+ *   reads ldim + 1 and writes ldim. */
+int nkv_sponge_fn(const nkv_layout* L, int ldim, const double* xm, const double* ym, const double* zm,
+                  const double* sections, unsigned active, double* fn, double* w, void* stream);
+int nkv_body_force(const nkv_layout* L, double* ff, const double* ff0, const double* fc, const double* f_re,
+                   const double* f_im, double c, double s, const double* fn, const double* ref, const double* v,
+                   double st, int n_vel, unsigned flags, void* stream);
 
 /* ---- eigenmode kinetic-energy budget (stability_energy_budget, postproc.f90:649-872; uparam(1) = 4.1) ----
  * lx1, ldim, D, xm, ym, zm: as nkv_gradm1 (ldim 2 or 3, lx1 <= 10, lx1^ldim points per element divide

@@ -34,6 +34,8 @@ NKV_MGS_LAGGED = 0x200
 NKV_CHECK_BREAKDOWN = 0x80
 NKV_SFD_MONITOR = 0x400
 NKV_TDF_STORE = 0x800
+NKV_BF_IMAG = 0x1000
+NKV_BF_PERTURBATION = 0x2000
 # enum nkv_vortex_criterion: a mask holds bit (1 << code); output slots ascend with the code
 (NKV_VC_VORTICITY, NKV_VC_LAMBDA2, NKV_VC_Q, NKV_VC_DELTA, NKV_VC_SWIRLING, NKV_VC_OMEGA, NKV_VC_SYMMETRIC,
  NKV_VC_ASSYMETRIC, NKV_VC_LAMBDA_CI, NKV_VC_COUNT) = range(10)
@@ -135,6 +137,8 @@ _SIGNATURES = {
                                     _P, c_int64, _P]),
     "nkv_filter_s0": (c_int, [_L, c_int, c_int, _P, _P, c_int64, c_int, _P, c_int64, _P]),
     "nkv_energy_components": (c_int, [_L, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P]),
+    "nkv_sponge_fn": (c_int, [_L, c_int, _P, _P, _P, POINTER(c_double), c_uint, _P, _P, _P]),
+    "nkv_body_force": (c_int, [_L, _P, _P, _P, _P, _P, c_double, c_double, _P, _P, _P, c_double, c_int, c_uint, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

@@ -22,6 +22,8 @@
 //   postproc.hip      eigenmode kinetic-energy budget: fused production terms + integrals, divergence, dissipation
 //   vortex.hip        flow diagnostics: fused vortex criteria (+ filter_s0 in LDS), standalone filter_s0,
 //                     energy / enstrophy component sums
+//   forcing.hip       body-force hooks: sponge function + masked dot weights, fused force assembly (SFD/TDF
+//                     forcing + harmonic resolvent forcing + sponge term) per time step
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -149,7 +149,7 @@ class SFD:
     mode, the reference's continuation branch — no filter, no forcing, only the residual);
     ``dt``: the time step; ``tol``: ``max(param(21), param(22))`` (:149); ``volume``: the domain
     volume ``volvm1`` of ``normvc``, default the all-reduced sum of the context's weights (exact when
-    they are ``bm1``; with sponge-zeroed ``bm1s`` pass the full volume).  ``normvc`` is Nek5000's, not
+    they are ``bm1``; with sponge-zeroed ``bm1s`` pass the full volume: ``Sponge.volume``).  ``normvc`` is Nek5000's, not
     part of the reference tree: its l2 is sqrt(sum_c glsc3(u_c, bm1, u_c) / volvm1) over the
     velocities, which is what ``step`` returns with the context's weights.  ``residu``: a path for the
     ``residu.dat`` records (rank 0).  ``monitors``: callables ``m(v, istep, time)`` run at the end of
