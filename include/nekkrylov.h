@@ -538,6 +538,52 @@ int nkv_body_force(const nkv_layout* L, double* ff, const double* ff0, const dou
                    const double* f_im, double c, double s, const double* fn, const double* ref, const double* v,
                    double st, int n_vel, unsigned flags, void* stream);
 
+/* ---- per-time-step monitors: surface forces and running statistics ---------------------------------------
+ * nkv_torque: nekStab_torque's integrals (utils.f90:758-864) over the member faces this shard owns, with
+ *   Nek5000's comp_sij, mappr, drgtrq and create_obj restated from their definitions.  The
+ *   cost scales with the number of member faces, not with n_v: one workgroup per face stages that
+ *   element in LDS, differentiates and interpolates only at the face's GLL points, and a fixed-order
+ *   second stage adds the members of every object.  No atomics.
+ *   lx1, ldim, D, xm, ym, zm, u, u_stride: as nkv_gradm1 (velocity component c at u + c u_stride).
+ *   wgll: the lx1 GLL weights.  faces: nfaces rows of 3 ints (element local to this shard, 0-based;
+ *   face 1..6 in the preprocessor's numbering, 1: s=-1, 2: r=+1, 3: s=+1, 4: r=-1, 5: t=-1, 6: t=+1;
+ *   object 1..nobj), once on the HOST (checked before any launch) and once on the device.
+ *   Pressure: pr (this shard's n_p mesh-2 values, lx2^ldim per element, interpolated to the face points
+ *   with Ipm, the lx1 x lx2 row-major matrix from the lx2 Gauss to the lx1 GLL points) or pm1 (a mesh-1
+ *   pressure of n_v points); exactly one of them.  Then pm += x dpdx + y dpdy [+ z dpdz] (:766-768).
+ *   visc_field (n_v points) or, when NULL, the scalar visc (param(2)).  x0, dp_mean: 3 doubles on the HOST.
+ *   Per face point (fp = a + lx1 b over the in-face directions in ascending order), no contraction:
+ *     nA_k = +-(cofactor_k w)           the outward normal times the area: glmapm1's cofactors of the face's
+ *                                       direction as nkv_gradm1 forms them, w the GLL face weight
+ *     s_ij = G_ij + G_ji                G: nkv_gradm1's gradient, bit for bit (no factor 1/2)
+ *     dg(k,1) = pm nA_k                 dg(k,2) = -nu ((s_k1 nA_1 + s_k2 nA_2) [+ s_k3 nA_3])
+ *     dg(:,3) = r x dg(:,1)             dg(:,4) = r x dg(:,2),  r = x - x0 (2-D: the z component only)
+ *   dgtq[face][3 l + k] = (the terms of the face added one by one in ascending fp) scale  (cmult, :811);
+ *   out[o][3 l + k], o = 1..nobj: lane m mod 64 adds the object's faces in ascending table row m onto 0.0,
+ *   the 64 lane sums meet in a butterfly (xor 32, 16, 8, 4, 2, 1); out[0]: the object rows added in
+ *   ascending o onto 0.0 (:839-864).  The caller all-reduces out (12 (nobj + 1) doubles: the reference's
+ *   twelve gop calls, :827-838) and, on more than one rank, forms row 0 again from the reduced rows.
+ *   sij_out (may be NULL): [face][3 | 6][fp] in comp_sij's order (s11, s22, s12 | s11, s22, s33, s12, s23,
+ *   s31); na_out (may be NULL): [face][ldim][fp].  nfaces = 0 or an empty shard: out is zeroed, no launch.
+ *   The unused glmin / glmax of :776-781 are not built.
+ * nkv_avg_step: nekStab_avg's update (postproc.f90:581-599) as one pass over every stored row of v:
+ *     avg = alpha avg + beta v                        avg1 (:582-586)
+ *     rms = alpha rms + (beta v) v                    avg2 (:590-594); rms NULL: ifstatis = .false.
+ *     uv, vw, wu = alpha m + (beta f) g               avg3 (:597-599, commented out in the reference):
+ *                                                     cross NULL or ncross fields of sv doubles, ncross = 1
+ *                                                     (uv) or 3 (uv, vw, wu), from the velocities in registers
+ *   avg and rms are vectors in the layout above.  Only live rows are written: padding rows and the time
+ *   slot are left alone.  v, avg, rms and the cross buffer must not overlap (NKV_EINVAL).
+ *   Streams of live rows: 1 read + 2 read-modify-writes per stored row, + 2 per cross moment. */
+int nkv_torque(const nkv_layout* L, int lx1, int lx2, int ldim, const double* D, const double* wgll,
+               const double* Ipm, const double* xm, const double* ym, const double* zm, const double* u,
+               int64_t u_stride, const double* pr, const double* pm1, const double* visc_field, double visc,
+               const int* faces_host, const int* faces_dev, int nfaces, int nobj, const double* x0,
+               const double* dp_mean, double scale, double* dgtq, double* out, double* sij_out, double* na_out,
+               void* stream);
+int nkv_avg_step(const nkv_layout* L, const double* v, double* avg, double* rms, double* cross, int ncross,
+                 double alpha, double beta, void* stream);
+
 /* ---- eigenmode kinetic-energy budget (stability_energy_budget, postproc.f90:649-872; uparam(1) = 4.1) ----
  * lx1, ldim, D, xm, ym, zm: as nkv_gradm1 (ldim 2 or 3, lx1 <= 10, lx1^ldim points per element divide
  * n_v, zm exactly when ldim = 3).  Every field is n_v points in Nek point order; strides are in doubles

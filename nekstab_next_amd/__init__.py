@@ -16,11 +16,13 @@ def __getattr__(name):
 
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
                 "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
-                "postproc", "vortex", "forcing", "_lib"):
+                "postproc", "vortex", "forcing", "monitors", "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
     if name in ("SFD", "TDF"):   # the fixed-point forcing classes (fixedp.py)
         return getattr(importlib.import_module(".fixedp", __name__), name)
     if name in ("Sponge", "SpongeConfig", "BodyForce"):   # the sponge and the body-force assembly (forcing.py)
         return getattr(importlib.import_module(".forcing", __name__), name)
+    if name in ("Torque", "TorqueMonitor", "Statistics"):   # the per-step monitors (monitors.py)
+        return getattr(importlib.import_module(".monitors", __name__), name)
     raise AttributeError(name)

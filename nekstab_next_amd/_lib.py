@@ -139,6 +139,9 @@ _SIGNATURES = {
     "nkv_energy_components": (c_int, [_L, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P]),
     "nkv_sponge_fn": (c_int, [_L, c_int, _P, _P, _P, POINTER(c_double), c_uint, _P, _P, _P]),
     "nkv_body_force": (c_int, [_L, _P, _P, _P, _P, _P, c_double, c_double, _P, _P, _P, c_double, c_int, c_uint, _P]),
+    "nkv_torque": (c_int, [_L, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_double,
+                           _P, _P, c_int, c_int, POINTER(c_double), POINTER(c_double), c_double, _P, _P, _P, _P, _P]),
+    "nkv_avg_step": (c_int, [_L, _P, _P, _P, _P, c_int, c_double, c_double, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

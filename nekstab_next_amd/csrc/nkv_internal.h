@@ -24,6 +24,8 @@
 //                     energy / enstrophy component sums
 //   forcing.hip       body-force hooks: sponge function + masked dot weights, fused force assembly (SFD/TDF
 //                     forcing + harmonic resolvent forcing + sponge term) per time step
+//   monitors.hip      per-step monitors: surface forces on the member faces of an object (lift / drag / torque),
+//                     running mean, mean-square and cross-moment statistics in one pass
 #pragma once
 
 #include <hip/hip_runtime.h>
