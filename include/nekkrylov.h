@@ -434,6 +434,23 @@ int nkv_group_average(int64_t n_groups, const int64_t* start, const int64_t* mem
 int nkv_symmetric_seed(const nkv_layout* L, const double* ym, const double* zm, double alpha, double* qx,
                        double* qz, double* qt, void* stream);
 
+/* ---- sharded gather-scatter (dssum + vmult / dsavg over element shards; host half: gs.py) --------
+ * Direct-stiffness averaging of nf field segments (1 <= nf <= NKV_GS_MAX_FIELDS; q: a HOST array of nf
+ * device pointers, each to n_v doubles) in one launch, with 32-bit indices (n_v <= INT32_MAX).
+ * nkv_gs_pack: send[f*stride + i] = q[f][send_idx[i]] for i < n_send <= stride (send: nf*stride doubles).
+ * nkv_gs_average: for CSR groups (start: n_groups+1 offsets into src) every group's entries are summed
+ * in entry order from 0.0, scaled by 1.0/count (no contraction: nkv_group_average's arithmetic), and
+ * the mean is written to the group's local entries.  An entry src >= 0 is a local point index; src < 0
+ * is -(1 + rank*stride + pos): segment f's value at recv[(rank*nf + f)*stride + pos], the n_ranks pack
+ * buffers gathered in rank order (n_ranks*stride <= INT32_MAX; recv may be NULL when stride = 0).
+ * Entries are in ascending global point number, so the result is bit-identical for any sharding.
+ * Both return NKV_OK without touching memory for a zero count. */
+#define NKV_GS_MAX_FIELDS 64
+int nkv_gs_pack(int nf, double* const* q, int64_t n_v, int64_t n_send, const int32_t* send_idx, int64_t stride,
+                double* send, void* stream);
+int nkv_gs_average(int nf, double* const* q, int64_t n_v, int64_t n_groups, const int32_t* start, const int32_t* src,
+                   const double* recv, int64_t stride, int n_ranks, void* stream);
+
 /* ---- ts_gmres host helper (a17, newton_krylov.f90:250-269) -------------------------------
  * The least-squares residual ||beta e_1 - H(1:k+2, 1:k+1) y|| after one more Hessenberg column, in
  * O(k) host work (Givens rotations; no device work, no stream).  h: H(0:k+1, k) (0-based column k,

@@ -21,6 +21,7 @@ NKV_ABI_VERSION = 3
 NKV_TILE = 4096
 NKV_MAX_COLS = 1024   # most columns per multi-dot (include/nekkrylov.h)
 NKV_ROT_MAX_OUT = 256   # most output columns of a basis rotation with more than 16 kept (include/nekkrylov.h)
+NKV_GS_MAX_FIELDS = 64   # most field segments per gather-scatter launch (include/nekkrylov.h)
 NKV_OK, NKV_EINVAL, NKV_EHIP, NKV_ENAN, NKV_ESHAPE, NKV_ECALLBACK, NKV_EBREAKDOWN = 0, 1, 2, 3, 4, 5, 6
 NKV_TIME = 0x1
 NKV_ACCUMULATE = 0x2
@@ -120,6 +121,8 @@ _SIGNATURES = {
     "nkv_mth_rand_add": (c_int, [_L, c_int, c_int, c_int, c_int64, _P, _P, _P, c_double, c_double, c_double, _P, _P]),
     "nkv_group_average": (c_int, [c_int64, _P, _P, _P, _P]),
     "nkv_symmetric_seed": (c_int, [_L, _P, _P, c_double, _P, _P, _P, _P]),
+    "nkv_gs_pack": (c_int, [c_int, POINTER(c_void_p), c_int64, c_int64, _P, c_int64, _P, _P]),
+    "nkv_gs_average": (c_int, [c_int, POINTER(c_void_p), c_int64, c_int64, _P, _P, _P, c_int64, c_int, _P]),
     "nkv_wavemaker": (c_int, [_L, _P, _P, _P, _P, _P, c_int, _P]),
     "nkv_gradm1": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int64, _P, c_int64, _P]),
     "nkv_bf_sensitivity": (c_int, [_L, _P, _P, _P, _P, _P, _P, c_int, _P]),

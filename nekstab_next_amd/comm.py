@@ -97,6 +97,32 @@ class Comm:
                 tm.end("allreduce", 8.0 * t.numel())
         return t
 
+    def allgather_(self, send: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """Every rank's ``send`` (equal sizes) into ``out`` (``world * send.numel()`` elements) in rank
+        order; a plain copy at world 1.  RCCL gathers the device buffers directly, stream-ordered.
+        gloo (the backend of the multi-rank tests; it does not gather device tensors) is staged
+        through the host: the bytes travel unchanged, where the alternative, an all-reduce of a
+        zero-filled buffer, would turn a -0.0 into +0.0."""
+        if out.numel() != self.world * send.numel() or out.dtype != send.dtype:
+            raise ValueError(f"allgather_: out holds {out.numel()} {out.dtype} values, "
+                             f"{self.world} x {send.numel()} {send.dtype} needed")
+        if not (self.world > 1 or self.force):
+            out.view(-1).copy_(send.view(-1))
+            return out
+        tm = self.timer
+        if tm is not None:
+            tm.begin("allgather")
+        if self.backend == "nccl":
+            dist.all_gather_into_tensor(out.view(-1), send.contiguous().view(-1), group=self.group)
+        else:
+            host = torch.empty(out.numel(), dtype=out.dtype)
+            dist.all_gather(list(host.view(self.world, -1).unbind(0)), send.detach().reshape(-1).cpu(),
+                            group=self.group)
+            out.view(-1).copy_(host)
+        if tm is not None:
+            tm.end("allgather", float(out.numel() * out.element_size()))
+        return out
+
     def devices(self, device=None) -> list:
         """Every rank's :func:`device_identity`, in rank order (a collective at world > 1)."""
         me = device_identity(device)

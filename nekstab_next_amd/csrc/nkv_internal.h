@@ -26,6 +26,8 @@
 //                     forcing + harmonic resolvent forcing + sponge term) per time step
 //   monitors.hip      per-step monitors: surface forces on the member faces of an object (lift / drag / torque),
 //                     running mean, mean-square and cross-moment statistics in one pass
+//   gs.hip            sharded gather-scatter: pack of the shared points, direct-stiffness average of many
+//                     field segments per launch from local points and the values other ranks sent
 #pragma once
 
 #include <hip/hip_runtime.h>

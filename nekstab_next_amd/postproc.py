@@ -12,8 +12,9 @@ Per mode the reference forms (all pointwise, then ``glsc2`` with the mass matrix
   each Laplacian being four ``gradm1`` + ``dsavg`` rounds of which it keeps a third (:853-872) — here one
   gradient of the 2 ldim mode components (``nkv_gradm1``), ``dsavg`` of every first derivative, one
   divergence (``nkv_divm1``), ``dsavg`` of the 2 ldim Laplacians and one fused term + integral
-  (``nkv_pke_dissipation``).  ``dsavg`` is linear, so averaging the sum d2x + d2y + d2z equals the
-  reference's sum of the three averages to rounding.
+  (``nkv_pke_dissipation``).  On several ranks ``gs.GatherScatter`` averages each round in one batch: two
+  exchanges per mode.  ``dsavg`` is linear, so averaging the sum d2x + d2y + d2z equals the reference's
+  sum of the three averages to rounding.
 
 The ten local integrals travel in one all-reduce.  In 2-D every term with a z factor (integrals 3, 6,
 7, 8, 9 and d2z) is absent, i.e. zero: the reference reads never-set arrays there.
@@ -51,7 +52,8 @@ def energy_budget_fields(ctx: NekContext, base: NekVector, dRe: NekVector, dIm: 
     [c][d] (``sv`` doubles each), ``diss`` one segment, ``integrals`` the ten ``glsc2(bm1, .)`` of the
     reference's ``energy_budget(:, 1..10)`` on the device, all-reduced (index 3c + d for P[c][d], 9 for
     the dissipation; the 2-D z entries stay zero).  ``face_average(ptr)`` is ``dsavg`` of one segment
-    in place (None skips it); ``bm1`` defaults to the context's weights."""
+    in place (a ``gs.GatherScatter`` averages each round's segments in one batch; None skips it);
+    ``bm1`` defaults to the context's weights."""
     lay = ctx.layout
     d, sv = lay.ldim, lay.sv
     f64 = dict(dtype=torch.float64, device=ctx.device)
@@ -67,14 +69,14 @@ def energy_budget_fields(ctx: NekContext, base: NekVector, dRe: NekVector, dIm: 
     gp = grad.data_ptr()
     grad_op(dRe.ptr, gp, nfld=d, u_stride=sv, g_stride=sv)
     grad_op(dIm.ptr, gp + 8 * d * d * sv, nfld=d, u_stride=sv, g_stride=sv)
-    if face_average is not None:
-        for q in range(2 * d * d):
-            face_average(gp + 8 * q * sv)
+    if face_average is not None:   # a GatherScatter: one batch (one exchange) per round, two per mode
+        from .gs import average_segments
+
+        average_segments(face_average, [gp + 8 * q * sv for q in range(2 * d * d)])
     lap = torch.zeros(2 * d * sv, **f64)        # [Re, Im][component]
     ctx.call("nkv_divm1", lay.lx1, d, D, xyz[0], xyz[1], zp, gp, 2 * d, sv, lap.data_ptr(), sv, ctx.stream)
     if face_average is not None:
-        for q in range(2 * d):
-            face_average(lap.data_ptr() + 8 * q * sv)
+        average_segments(face_average, [lap.data_ptr() + 8 * q * sv for q in range(2 * d)])
     diss = torch.zeros(sv, **f64)
     ctx.call("nkv_pke_dissipation", dRe.ptr, dIm.ptr, sv, lap.data_ptr(), sv, d, float(nu), w.data_ptr(),
              diss.data_ptr(), local.data_ptr() + 8 * 12, ctx.ws.data_ptr(), ctx.stream)
@@ -112,9 +114,9 @@ def stability_energy_budget(ctx: NekContext, directory: str, coords: dict, sessi
 
     ``normalize``: "reference" multiplies both parts by alpha as the reference does (``nopcmult``, :707-708,
     under a comment that says normalise); "unit" divides; None leaves the mode as loaded.
-    ``face_average``: "auto" (one-rank ``seeds.FaceAverage``; refused at world > 1), a callable
-    ``f(ptr)`` (the case's gather-scatter on one field segment) or None.  ``bm1``: the mass matrix
-    (n_v local values; default the context's weights, which differ from it only inside a sponge).
+    ``face_average``: "auto" (``seeds.FaceAverage`` on one rank, ``gs.GatherScatter`` on several), a
+    ``gs.GatherScatter``, a callable ``f(ptr)`` (dsavg of one field segment) or None.  ``bm1``: the mass
+    matrix (n_v local values; default the context's weights, which differ from it only inside a sponge).
     Returns one dict per mode: integrals (10), total, balance, alpha, paths (and the fields of this rank's
     points: production [c][d], dissipation)."""
     from . import fld
@@ -127,9 +129,9 @@ def stability_energy_budget(ctx: NekContext, directory: str, coords: dict, sessi
     if isinstance(face_average, str):
         if face_average != "auto":
             raise ValueError("face_average: 'auto', a callable f(ptr) or None")
-        from .seeds import FaceAverage
+        from .gs import auto_average
 
-        face_average = FaceAverage(ctx, coords).apply
+        face_average = auto_average(ctx, coords)
     grad_op = Gradm1(ctx, coords)
     w = _bm1_tensor(ctx, bm1)
 

@@ -10,7 +10,8 @@ default (core/main.f90:29); the noise is ``op_add_noise`` / ``add_noise_scal`` (
 * Nek5000's ``dssum`` + ``vmult`` (direct-stiffness averaging of the points elements share) and
   ``dsavg`` are restated on one rank from the coordinates (``FaceAverage``: groups of coincident
   points, averaged on the device by ``nkv_group_average``).  On several ranks the points on a
-  shard boundary would need Nek's gather-scatter across ranks: pass your own ``face_average``;
+  shard boundary are shared across ranks: pass a ``gs.GatherScatter`` as ``face_average`` (the same
+  groups and arithmetic over the shards, bit-identical to the one-rank average);
 * ``bcdirVC`` / ``bcdirSC`` (Dirichlet masks: walls, inflow) need the case's boundary conditions,
   which field files do not hold: pass them as ``mask`` (a vector of 0/1 multipliers, 1 elsewhere).
 
@@ -74,7 +75,23 @@ def coincident_groups(coords: dict, rel_tol: float = 1e-9) -> tuple[np.ndarray, 
     if n == 0:
         return np.zeros(1, np.int64), np.zeros(0, np.int64)
     ext = max(float(np.ptp(x)) for x in xs) or 1.0
-    tol = rel_tol * ext
+    gid = group_ids(xs, rel_tol * ext)
+    counts = np.bincount(gid)
+    idx = np.flatnonzero(counts[gid] > 1)                 # ascending point order
+    members = idx[np.lexsort((idx, gid[idx]))].astype(np.int64)
+    g_multi = gid[members]
+    starts = np.flatnonzero(np.r_[True, g_multi[1:] != g_multi[:-1]]) if members.size else np.zeros(0, np.int64)
+    return np.r_[starts, members.size].astype(np.int64), members
+
+
+def group_ids(xs, tol: float) -> np.ndarray:
+    """The grouping rule of :func:`coincident_groups` on its own: one group id per point (singletons
+    included) for coordinate arrays ``xs`` and cells of ``tol``.  The cells are absolute (x / tol
+    rounded), so any subset of the points grouped with the same ``tol`` lands in the same cells —
+    what the sharded gather-scatter (``gs.py``) relies on."""
+    n = xs[0].size
+    if n == 0:
+        return np.zeros(0, np.int64)
     sc = [x / tol for x in xs]
     keys = [np.round(v).astype(np.int64) for v in sc]
     order = np.lexsort(keys[::-1])
@@ -116,12 +133,7 @@ def coincident_groups(coords: dict, rel_tol: float = 1e-9) -> tuple[np.ndarray, 
             lut = np.arange(int(gid.max()) + 1, dtype=np.int64)
             lut[moved] = np.array([roots[g] for g in moved.tolist()], dtype=np.int64)
             gid = lut[gid]
-    counts = np.bincount(gid)
-    idx = np.flatnonzero(counts[gid] > 1)                 # ascending point order
-    members = idx[np.lexsort((idx, gid[idx]))].astype(np.int64)
-    g_multi = gid[members]
-    starts = np.flatnonzero(np.r_[True, g_multi[1:] != g_multi[:-1]]) if members.size else np.zeros(0, np.int64)
-    return np.r_[starts, members.size].astype(np.int64), members
+    return gid
 
 
 class FaceAverage:

@@ -16,8 +16,9 @@ kernel, ``nkv_wavemaker``) and write it as the temperature field of ``wm_<sessio
 Nek5000's ``gradm1`` of every velocity component of the four modes (``nkv_gradm1``: one element per
 LDS tile, the geometric factors recomputed from the GLL coordinates on the fly, so a gradient reads
 the coordinates and the field once and writes its ldim components), ``dsavg`` of each gradient
-(direct-stiffness averaging: ``seeds.FaceAverage`` on one rank, the caller's gather-scatter on
-several), the pointwise terms tr, ti, pr, pi and sr = tr + pr, si = ti + pi in one streaming kernel
+(direct-stiffness averaging: ``seeds.FaceAverage`` on one rank, ``gs.GatherScatter`` over the shards on
+several, all gradients of a round in one batch), the pointwise terms tr, ti, pr, pi and sr = tr + pr,
+si = ti + pi in one streaming kernel
 (``nkv_bf_sensitivity``), written as the velocity of ``tr_``, ``ti_``, ``pr_``, ``pi_``, ``sr_``,
 ``si_<session>0.f00001`` — the files ``ts_steady_force_sensitivity`` reads back (sr/si).
 
@@ -228,8 +229,9 @@ BF_OUTPUTS = ("tr_", "ti_", "pr_", "pi_", "sr_", "si_")
 def bf_sensitivity_fields(ctx: NekContext, dRe: NekVector, dIm: NekVector, aRe: NekVector, aIm: NekVector,
                           grad_op: Gradm1, face_average=None) -> tuple[torch.Tensor, torch.Tensor]:
     """sensitivity.f90:170-259 on bi-orthogonalised velocity-only vectors: gradm1 + dsavg of the
-    4 x ldim components (``face_average(ptr)`` averages one field segment in place; None skips
-    dsavg), then the pointwise terms.  Returns (out, grad): out holds 6 x ldim field segments
+    4 x ldim components (``face_average(ptr)`` averages one field segment in place; a
+    ``gs.GatherScatter`` averages all of them in one batch; None skips dsavg), then the pointwise
+    terms.  Returns (out, grad): out holds 6 x ldim field segments
     [tr, ti, pr, pi, sr, si][component], grad 4 x ldim x ldim [mode][component][direction]."""
     lay = ctx.layout
     d, sv = lay.ldim, lay.sv
@@ -238,9 +240,10 @@ def bf_sensitivity_fields(ctx: NekContext, dRe: NekVector, dIm: NekVector, aRe: 
     gp = grad.data_ptr()
     for md, v in enumerate((dRe, dIm, aRe, aIm)):   # one launch per mode: its d components together
         grad_op(v.ptr, gp + 8 * md * d * d * sv, nfld=d, u_stride=sv, g_stride=sv)
-    if face_average is not None:
-        for q in range(4 * d * d):
-            face_average(gp + 8 * q * sv)
+    if face_average is not None:   # a GatherScatter: all the gradients in one batch (one exchange per round)
+        from .gs import average_segments
+
+        average_segments(face_average, [gp + 8 * q * sv for q in range(4 * d * d)])
     ctx.call("nkv_bf_sensitivity", dRe.ptr, dIm.ptr, aRe.ptr, aIm.ptr, gp, out.data_ptr(), d, ctx.stream)
     return out, grad
 
@@ -252,9 +255,10 @@ def bf_sensitivity(ctx: NekContext, directory: str, coords: dict, session: str =
     (:170-199) and the terms (:202-235, 258-259) on the device, then ``outpost`` of the velocity of
     tr_, ti_, pr_, pi_, sr_, si_<session><rank>.f00001 into ``outdir`` (default ``directory``;
     ``ifto = ifpo = .false.``, :138; header time of the last file loaded).  ``coords``: this rank's
-    GLL coordinates (``seeds.coords_from_fld``).  ``face_average``: "auto" = one-rank averaging
-    over coincident points (``seeds.FaceAverage``; refused at world > 1), a callable ``f(ptr)``
-    (the case's gather-scatter on one field segment), or None (no dsavg).  Returns the six
+    GLL coordinates (``seeds.coords_from_fld``).  ``face_average``: "auto" = averaging over
+    coincident points (``seeds.FaceAverage`` on one rank, ``gs.GatherScatter`` on several), a
+    ``gs.GatherScatter``, a callable ``f(ptr)`` (dsavg of one field segment), or None (no dsavg).
+    Returns the six
     outputs (this rank's points, [component] arrays), <adjoint, direct>_W and the files."""
     from . import fld
 
@@ -263,9 +267,9 @@ def bf_sensitivity(ctx: NekContext, directory: str, coords: dict, session: str =
     if isinstance(face_average, str):
         if face_average != "auto":
             raise ValueError("face_average: 'auto', a callable f(ptr) or None")
-        from .seeds import FaceAverage
+        from .gs import auto_average
 
-        face_average = FaceAverage(ctx, coords).apply
+        face_average = auto_average(ctx, coords)
     ip = biorthogonalize(ctx, dRe, dIm, aRe, aIm)
     out, _ = bf_sensitivity_fields(ctx, dRe, dIm, aRe, aIm, Gradm1(ctx, coords), face_average)
     ctx.check_nan()

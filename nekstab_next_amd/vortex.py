@@ -177,16 +177,17 @@ class VortexCore:
             if average != "auto":
                 raise ValueError("average: 'auto', a callable f(ptr) or None")
             if self._auto is None:
-                from .seeds import FaceAverage
+                from .gs import auto_average
 
-                self._auto = FaceAverage(self.ctx, self.coords).apply    # refused at world > 1
+                self._auto = auto_average(self.ctx, self.coords)   # FaceAverage at world 1, else GatherScatter
             return self._auto, "auto"
         return average, average
 
     def comp_vort3(self, vec: NekVector, average="auto", bm1=None) -> torch.Tensor:
         """Nek5000's ``comp_vort3``: the curl of the velocity of ``vec``, then dssum(bm1 w) / dssum(bm1)
         as two applications of ``average(ptr)`` (``dsavg`` of one segment in place, e.g.
-        ``seeds.FaceAverage.apply``; "auto": the one-rank average, refused at world > 1; None: the raw
+        ``seeds.FaceAverage.apply``; "auto": ``FaceAverage`` on one rank, ``gs.GatherScatter`` over the
+        shards on several; a ``GatherScatter`` averages the components in one batch; None: the raw
         element-local curl).  The averaged ``bm1`` is computed once per ``average``.  ``bm1``: the mass
         matrix (default the context's weights).  Returns a (1 or 3, sv) tensor."""
         from .postproc import _bm1_tensor
@@ -195,15 +196,25 @@ class VortexCore:
         w = self.criteria(vec, ["vorticity"], filtered=False)["vorticity"]
         if average is None:
             return w
+        from .gs import as_gather_scatter
+
         fn, key = self._average(average)
+        gs = as_gather_scatter(fn)   # collective at world > 1: an empty shard takes part too
         n = lay.n_v
         b = _bm1_tensor(ctx, bm1)[:n]
         if key not in self._denominators or self._denominators[key][0] is not bm1:
             den = b.clone()
-            if n:
+            if gs is not None:
+                gs.apply(den.data_ptr())
+            elif n:
                 fn(den.data_ptr())
             self._denominators[key] = (bm1, den)
         den = self._denominators[key][1]
+        if gs is not None:   # the components in one batch: one exchange
+            w[:, :n] *= b
+            gs.apply_many([w[c].data_ptr() for c in range(self.n_vort)])
+            w[:, :n] /= den[:n]
+            return w
         for c in range(self.n_vort):
             row = w[c]
             row[:n] *= b
