@@ -706,6 +706,44 @@ int nkv_filter_s0(const nkv_layout* L, int lx1, int ldim, const double* F, const
 int nkv_energy_components(const nkv_layout* L, const double* w, const double* f, int64_t f_stride, int ncomp,
                           const double* t, const double* y, double* sums_dev, void* ws, void* stream);
 
+/* ---- spectral-element advection-diffusion of the dotted fields by a frozen base flow ----------------
+ * The equation Nek5000 advances for a passive scalar (ifheat, t), applied to every weighted field on its
+ * own: the model operator whose matvec is a time integration over the mesh (LightKrylov's abstract_linop /
+ * exponential_prop, linear_operators.f90:39-103, whose body in nekStab is a Nek5000 run).  lx1, ldim, D, xm,
+ * ym, zm and the field conventions: as for the energy budget above; w: the lx1 GLL weights (device).  All
+ * arithmetic is f64 without contraction; no host synchronisation, no atomics, 64-bit point offsets,
+ * element-local (an element sub-range gives the bits of the whole).  A bad argument returns NKV_EINVAL with
+ * a message naming it; an empty shard (n_v = 0) returns NKV_OK and reads no pointer.
+ *
+ * nkv_advdiff_rhs: the LOCAL (unassembled) weak-form right-hand side of nfld fields (field f at
+ *   u + f*u_stride, result at r + f*r_stride, diffusivity kappa[f]: nfld doubles on the DEVICE) in one tiled
+ *   pass.  With g[d][a], jac the geometric factors of nkv_gradm1 (glmapm1 / xyzrst), d_d u the derivative
+ *   as nkv_gradm1 forms it, bm1 = jac w_i w_j [w_k] and D_a^T the transposed line sum along r, s, [t]:
+ *     forward:  r = -bm1 (U . grad u) + sum_a D_a^T [ sum_d (g[d][a]/jac) (-kappa bm1 d_d u) ]
+ *     adjoint:  r =                     sum_a D_a^T [ sum_d (g[d][a]/jac) (-kappa bm1 d_d u - bm1 U_d u) ]
+ *   U: the base flow, component d at U + d*U_stride.  The two are transposes of each other as matrices on
+ *   the local points.  Gradient and fluxes stay in LDS (lx1^2 + (ldim + 1) nt doubles, 32,800 bytes at
+ *   lx1 = 10 in 3-D).  r must not be u.  The operator is L u = minv dsavg(r), minv = mask / dsavg(bm1):
+ *   Nek5000's binvm1 dssum(r) written with dsavg, as comp_vort3 does.
+ * nkv_advdiff_bm1: bm1[p] = jac w_i w_j [w_k] (Nek5000's bm1, coef.f), the product the right-hand side
+ *   forms, n_v doubles.
+ * nkv_advdiff_stage: w_f = v_f + c (minv r_f) for nfld fields in one launch (field f at v + f*v_stride,
+ *   r + f*r_stride, w + f*w_stride; minv: n_v doubles): one Horner stage of RK4's polynomial
+ *   p(dt L) = 1 + dt L (1 + dt L / 2 (1 + dt L / 3 (1 + dt L / 4))).  v = NULL stands for zero: with
+ *   c = 1 the two pointwise halves of the projector x -> minv dsavg(bm1 x).  w may be v.  zero_rest != 0
+ *   (w a whole state vector: nfld = n_wf, w_stride = sv) also zeroes the n_p pressure rows and the time
+ *   slot of w, as nkv_op_rot2 does for time; padding rows are never written.  16-byte accesses when every
+ *   base and stride allows, the same bits either way. */
+int nkv_advdiff_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, const double* U, int64_t U_stride, const double* kappa,
+                    const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
+                    void* stream);
+int nkv_advdiff_bm1(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, double* bm1, void* stream);
+int nkv_advdiff_stage(const nkv_layout* L, const double* v, int64_t v_stride, const double* minv, const double* r,
+                      int64_t r_stride, double c, double* w, int64_t w_stride, int nfld, int zero_rest,
+                      void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

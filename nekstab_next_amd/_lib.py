@@ -145,6 +145,10 @@ _SIGNATURES = {
     "nkv_torque": (c_int, [_L, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_double,
                            _P, _P, c_int, c_int, POINTER(c_double), POINTER(c_double), c_double, _P, _P, _P, _P, _P]),
     "nkv_avg_step": (c_int, [_L, _P, _P, _P, _P, c_int, c_double, c_double, _P]),
+    "nkv_advdiff_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int64, _P, c_int64,
+                                c_int, _P]),
+    "nkv_advdiff_bm1": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "nkv_advdiff_stage": (c_int, [_L, _P, c_int64, _P, _P, c_int64, c_double, _P, c_int64, c_int, c_int, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

@@ -1,0 +1,348 @@
+// advdiff.hip — the spectral-element advection-diffusion of every dotted field by a frozen base flow U,
+// the equation Nek5000 advances for a passive scalar (ifheat, t) and the model operator behind
+// advdiff.AdvectionDiffusion (a LightKrylov abstract_linop whose matvec is a time integration,
+// linear_operators.f90:39-103).  Weak form on the GLL mesh, per element and field u with diffusivity kappa:
+//   forward:  r = -bm1 (U . grad u) + sum_a D_a^T [ sum_d (g[d][a] / jac) (-kappa bm1 d_d u) ]
+//   adjoint:  r =                     sum_a D_a^T [ sum_d (g[d][a] / jac) (-kappa bm1 d_d u - bm1 U_d u) ]
+// with g[d][a], jac the geometric factors of k_gradm1 (glmapm1 / xyzrst), d_d u the derivative exactly as
+// k_gradm1 forms it, bm1 = jac w_i w_j [w_k] the mass matrix and D_a^T the transposed line sum along the
+// reference direction a.  r is the LOCAL (unassembled) right-hand side: dssum and the inverse mass matrix
+// follow as dsavg and the pointwise k_advdiff_stage.  No contraction; element-local, so it shards with the
+// elements and any element sub-range gives the bits of the whole.
+#include "nkv_internal.h"
+
+namespace {
+
+// This thread's point inside its element and the product of its GLL weights.
+template <int LDIM, int NX>
+struct PointIndex {
+    int i, j, k;
+    __device__ __forceinline__ explicit PointIndex(int tid) {
+        constexpr int pts = tile_pts<LDIM, NX>();
+        const int r = tid % pts;
+        i = r % NX;
+        j = (r / NX) % NX;
+        k = LDIM == 3 ? r / (NX * NX) : 0;
+    }
+    __device__ __forceinline__ double weight(const double* w) const {
+#pragma clang fp contract(off)
+        const double wij = w[i] * w[j];
+        return LDIM == 3 ? wij * w[k] : wij;
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// The fused right-hand side: the tile of k_gradm1 (whole elements per workgroup, one point per thread).
+// The coordinates of a group of elements are staged in LDS and the factors formed once per group; then for
+// every field: stage u, differentiate by line sums, write the LDIM reference-space fluxes
+//   F_a = sum_d (g[d][a] / jac) G_d,   G_d = -kappa bm1 d_d u  [adjoint: - bm1 U_d u]
+// over the coordinate tiles (their last reader, the factors, is a barrier behind), barrier, take the
+// transposed line sums  sum_m D(m, i) F_r(m, j, k) + sum_m D(m, j) F_s(i, m, k) [+ sum_m D(m, k) F_t(i, j, m)]
+// and store r once.  Neither the gradient nor the fluxes touch global memory.  LDS: lx1^2 + (LDIM + 1) nt
+// doubles, 32,800 bytes at lx1 = 10 in 3-D.  Line sums unrolled by 2, as k_gradm1 measured.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX, bool ADJ>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_advdiff_rhs(
+    int64_t nel, int epb, int nfld, const double* __restrict__ Dg, const double* __restrict__ wg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ ub, int64_t b_stride, const double* __restrict__ kappa, const double* __restrict__ u,
+    int64_t u_stride, double* __restrict__ r, int64_t r_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    const int nt = epb * pts;
+    double* D = lds;                         // D(i, m) at D[i*NX + m]
+    double* X = D + NX * NX;                 // coordinates, then the flux along r
+    double* Y = X + nt;                      // ... along s
+    double* Z = Y + nt;                      // ... along t (3-D only)
+    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const PointIndex<LDIM, NX> ix(tid);
+    const double wt = ix.weight(wg);
+    const int le = tid / pts;
+    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = D + ix.j;
+    const double* Dck = D + ix.k;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double jacmi = 1.0 / jac;
+        const double bm = jac * wt;
+        double Ub[LDIM];
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) Ub[d] = live ? ub[d * b_stride + p] : 0.0;
+        for (int f = 0; f < nfld; ++f) {
+            if (f > 0) __syncthreads();   // every lane is done reading the previous field and its fluxes
+            if (live) U[tid] = u[f * u_stride + p];
+            __syncthreads();              // (and every lane has formed its factors: the tiles are free)
+            double adv = 0.0;
+            if (live) {
+                double ur, us, ut;
+                line_sums<LDIM, NX>(q, U, ur, us, ut);
+                const double kb = -kappa[f] * bm;
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
+                    if constexpr (ADJ) {
+                        G[d] = kb * du - bm * Ub[d] * U[tid];
+                    } else {
+                        G[d] = kb * du;
+                        adv = adv + Ub[d] * du;
+                    }
+                }
+                double* tiles[3] = {X, Y, Z};
+#pragma unroll
+                for (int a = 0; a < LDIM; ++a) {
+                    double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+                    tiles[a][tid] = F;
+                }
+            }
+            __syncthreads();
+            if (live) {
+                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+                for (int m = 1; m < NX; ++m) {
+                    tr = tr + Dci[m * NX] * X[q.ri + m];
+                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+                }
+                double acc = tr + ts;
+                if constexpr (LDIM == 3) {
+                    double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+                    acc = acc + tt;
+                }
+                r[f * r_stride + p] = ADJ ? acc : acc - bm * adv;
+            }
+        }
+    }
+}
+
+// bm1 = jac w_i w_j [w_k]: the factors' Jacobian times the GLL weights, the product the right-hand side forms.
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_advdiff_bm1(
+    int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ wg, const double* __restrict__ xm,
+    const double* __restrict__ ym, const double* __restrict__ zm, double* __restrict__ bm1) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int nt = epb * pts;
+    double* D = lds;
+    double* X = D + NX * NX;
+    double* Y = X + nt;
+    double* Z = Y + nt;
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const double wt = PointIndex<LDIM, NX>(tid).weight(wg);
+    const int le = tid / pts;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        if (live) bm1[p] = jac * wt;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// One Horner stage of p(dt L) for all fields (grid.y = field):  w_f = v_f + c (m r_f),  m the pointwise
+// inverse assembled mass matrix (mask / dsavg(bm1)) and r_f the averaged right-hand side.  v = NULL stands
+// for zero, which makes the same kernel the two pointwise halves of the projector: bm1 x before the
+// average, minv times the average after it (c = 1).  w may be v (pointwise).  On request field 0's blocks
+// also zero the pressure rows and the time slot of w, as k_op_rot2 zeroes y[time_off].  VEC: two points
+// per thread by 16-byte accesses; the odd last point goes to one thread.  No contraction, so both forms
+// give the same bits.
+// ------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_advdiff_stage(int64_t n, const double* v, int64_t v_stride,
+                                                            const double* __restrict__ m, const double* r,
+                                                            int64_t r_stride, double c, double* w, int64_t w_stride,
+                                                            double* zero_p, int64_t n_p, double* zero_t) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.y;
+    const double* vf = v ? v + f * v_stride : nullptr;
+    const double* rf = r + f * r_stride;
+    double* wf = w + f * w_stride;
+    const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+    auto point = [&](int64_t p) {
+        const double t = c * (m[p] * rf[p]);
+        wf[p] = vf ? vf[p] + t : t;
+    };
+    if constexpr (VEC) {
+        const int64_t pairs = n / 2;
+        for (int64_t i = t0; i < pairs; i += step) {
+            const int64_t p = 2 * i;
+            const double2 mm = ld2(m + p), rr = ld2(rf + p);
+            double2 o = make_double2(c * (mm.x * rr.x), c * (mm.y * rr.y));
+            if (vf) {
+                const double2 vv = ld2(vf + p);
+                o = make_double2(vv.x + o.x, vv.y + o.y);
+            }
+            st2(wf + p, o);
+        }
+        if ((n & 1) && t0 == 0) point(n - 1);
+    } else {
+        for (int64_t p = t0; p < n; p += step) point(p);
+    }
+    if (f == 0 && zero_p) {
+        for (int64_t p = t0; p < n_p; p += step) zero_p[p] = 0.0;
+        if (t0 == 0) *zero_t = 0.0;
+    }
+}
+
+template <int LDIM, int NX>
+void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
+                const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
+                int64_t u_stride, double* r, int64_t r_stride, int adjoint, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 1) * epb * pts);
+    static_assert(sizeof(double) * (10 * 10 + 4 * 1000) <= 65536, "dynamic LDS within 64 KiB at lx1 = 10");
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    if (adjoint)
+        hipLaunchKernelGGL((k_advdiff_rhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
+                           nfld, D, w, xm, ym, zm, ub, b_stride, kappa, u, u_stride, r, r_stride);
+    else
+        hipLaunchKernelGGL((k_advdiff_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
+                           epb, nfld, D, w, xm, ym, zm, ub, b_stride, kappa, u, u_stride, r, r_stride);
+}
+
+template <int LDIM, int NX>
+void launch_bm1(int64_t nel, const double* D, const double* w, const double* xm, const double* ym, const double* zm,
+                double* bm1, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)LDIM * epb * pts);
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    hipLaunchKernelGGL((k_advdiff_bm1<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, w, xm,
+                       ym, zm, bm1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nkv_advdiff_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, const double* U, int64_t U_stride, const double* kappa,
+                    const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
+                    void* stream) {
+    static const char who[] = "advdiff_rhs";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    if (nfld < 1) return fail(NKV_EINVAL, "%s: nfld=%d < 1", who, nfld);
+    if (U_stride < L->n_v || u_stride < L->n_v || r_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: strides U_stride=%lld u_stride=%lld r_stride=%lld below n_v=%lld", who,
+                    (long long)U_stride, (long long)u_stride, (long long)r_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(U, who, "U"));
+    CHECK(need(kappa, who, "kappa"));
+    CHECK(need(u, who, "u"));
+    CHECK(need(r, who, "r"));
+    if (u == r) return fail(NKV_EINVAL, "%s cannot run in place (r is u)", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_AD_RHS(NX)                                                                                            \
+    case NX:                                                                                                      \
+        if (ldim == 3)                                                                                            \
+            launch_rhs<3, NX>(nel, nfld, D, w, xm, ym, zm, U, U_stride, kappa, u, u_stride, r, r_stride, adjoint, \
+                              st);                                                                                \
+        else                                                                                                      \
+            launch_rhs<2, NX>(nel, nfld, D, w, xm, ym, zm, U, U_stride, kappa, u, u_stride, r, r_stride, adjoint, \
+                              st);                                                                                \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_AD_RHS) }
+#undef NKV_AD_RHS
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_advdiff_bm1(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, double* bm1, void* stream) {
+    static const char who[] = "advdiff_bm1";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(bm1, who, "bm1"));
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_AD_BM1(NX)                                                          \
+    case NX:                                                                    \
+        if (ldim == 3) launch_bm1<3, NX>(nel, D, w, xm, ym, zm, bm1, st);       \
+        else launch_bm1<2, NX>(nel, D, w, xm, ym, zm, bm1, st);                 \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_AD_BM1) }
+#undef NKV_AD_BM1
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_advdiff_stage(const nkv_layout* L, const double* v, int64_t v_stride, const double* minv, const double* r,
+                      int64_t r_stride, double c, double* w, int64_t w_stride, int nfld, int zero_rest,
+                      void* stream) {
+    static const char who[] = "advdiff_stage";
+    CHECK(check_layout(L));
+    const int64_t n = L->n_v;
+    if (n == 0) return NKV_OK;   // an empty shard: nothing to touch
+    if (nfld < 1 || nfld > 65535) return fail(NKV_EINVAL, "%s: nfld=%d outside 1..65535", who, nfld);
+    if ((v && v_stride < n) || r_stride < n || w_stride < n)
+        return fail(NKV_EINVAL, "%s: strides v_stride=%lld r_stride=%lld w_stride=%lld below n_v=%lld", who,
+                    (long long)v_stride, (long long)r_stride, (long long)w_stride, (long long)n);
+    CHECK(need(minv, who, "minv"));
+    CHECK(need(r, who, "r"));
+    CHECK(need(w, who, "w"));
+    if (!std::isfinite(c)) return fail(NKV_EINVAL, "%s: c=%g", who, c);
+    if (zero_rest && (nfld != L->n_wf || w_stride != L->sv))
+        return fail(NKV_EINVAL, "%s: zero_rest needs w to be a state vector (nfld=%d, n_wf=%d, w_stride=%lld, sv=%lld)",
+                    who, nfld, L->n_wf, (long long)w_stride, (long long)L->sv);
+    auto a16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const bool vec = a16(minv) && a16(r) && a16(w) && (!v || (a16(v) && v_stride % 2 == 0)) && r_stride % 2 == 0 &&
+                     w_stride % 2 == 0 && n >= 2;
+    double* zp = zero_rest ? w + (int64_t)L->n_wf * L->sv : nullptr;
+    double* zt = zero_rest ? w + rows_of(L) : nullptr;
+    const dim3 grid(grid_for(vec ? n / 2 : n, 1024), nfld);
+    if (vec)
+        hipLaunchKernelGGL(k_advdiff_stage<true>, grid, dim3(kThreads), 0, S(stream), n, v, v_stride, minv, r, r_stride, c,
+                           w, w_stride, zp, L->n_p, zt);
+    else
+        hipLaunchKernelGGL(k_advdiff_stage<false>, grid, dim3(kThreads), 0, S(stream), n, v, v_stride, minv, r, r_stride,
+                           c, w, w_stride, zp, L->n_p, zt);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+}  // extern "C"

@@ -28,6 +28,8 @@
 //                     running mean, mean-square and cross-moment statistics in one pass
 //   gs.hip            sharded gather-scatter: pack of the shared points, direct-stiffness average of many
 //                     field segments per launch from local points and the values other ranks sent
+//   advdiff.hip       spectral-element advection-diffusion of the dotted fields by a frozen base flow: fused
+//                     weak-form right-hand side (forward and adjoint), mass matrix, Horner stage / projector halves
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -349,8 +351,8 @@ struct TilePoint {
 // k_gradm1, operation for operation (mxm line sums with m ascending, addcol4 / subcol4 Jacobian,
 // ascol5 cofactors).  g[direction][reference coordinate r, s, t].
 template <int LDIM, int NX>
-__device__ __forceinline__ void geometric_factors(const TilePoint<LDIM, NX>& q, const double* X, const double* Y,
-                                                  const double* Z, double (&g)[3][3], double& jacmi) {
+__device__ __forceinline__ void geometric_factors_jac(const TilePoint<LDIM, NX>& q, const double* X, const double* Y,
+                                                      const double* Z, double (&g)[3][3], double& jac_out) {
 #pragma clang fp contract(off)
     constexpr int sj = NX, sk = NX * NX;
     const double *Di = q.Di, *Dj = q.Dj, *Dk = q.Dk;
@@ -372,7 +374,7 @@ __device__ __forceinline__ void geometric_factors(const TilePoint<LDIM, NX>& q, 
         g[1][0] = -xs;
         g[0][1] = -yr;
         g[1][1] = xr;
-        jacmi = 1.0 / jac;
+        jac_out = jac;
     } else {
         double zr = Di[0] * Z[ri], zs = Z[si] * Dj[0];
         double xt = X[ti] * Dk[0], yt = Y[ti] * Dk[0], zt = Z[ti] * Dk[0];
@@ -400,8 +402,18 @@ __device__ __forceinline__ void geometric_factors(const TilePoint<LDIM, NX>& q, 
         g[0][2] = yr * zs - ys * zr;   // tx
         g[1][2] = xs * zr - xr * zs;   // ty
         g[2][2] = xr * ys - xs * yr;   // tz
-        jacmi = 1.0 / jac;
+        jac_out = jac;
     }
+}
+
+// ... and the inverse Jacobian every derivative is scaled by (jacmi = 1 / jac, as k_gradm1 forms it).
+template <int LDIM, int NX>
+__device__ __forceinline__ void geometric_factors(const TilePoint<LDIM, NX>& q, const double* X, const double* Y,
+                                                  const double* Z, double (&g)[3][3], double& jacmi) {
+#pragma clang fp contract(off)
+    double jac;
+    geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+    jacmi = 1.0 / jac;
 }
 
 // ur, us, [ut] of one staged field at this point (k_gradm1's line sums).

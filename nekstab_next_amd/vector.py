@@ -63,7 +63,10 @@ class NekContext:
         if weights is None:
             self.w[: layout.n_v] = 1.0
         else:
-            wt = torch.as_tensor(np.asarray(weights, dtype=np.float64)).to(self.device)
+            if isinstance(weights, torch.Tensor):   # already on a device (e.g. AdvectionDiffusion.bm1)
+                wt = weights.detach().to(self.device, torch.float64).reshape(-1)
+            else:
+                wt = torch.as_tensor(np.asarray(weights, dtype=np.float64)).to(self.device)
             if wt.numel() != layout.n_v:
                 raise ValueError(f"weights: expected {layout.n_v} local values, got {wt.numel()}")
             self.w[: layout.n_v] = wt
