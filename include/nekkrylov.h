@@ -733,7 +733,23 @@ int nkv_energy_components(const nkv_layout* L, const double* w, const double* f,
  *   c = 1 the two pointwise halves of the projector x -> minv dsavg(bm1 x).  w may be v.  zero_rest != 0
  *   (w a whole state vector: nfld = n_wf, w_stride = sv) also zeroes the n_p pressure rows and the time
  *   slot of w, as nkv_op_rot2 does for time; padding rows are never written.  16-byte accesses when every
- *   base and stride allows, the same bits either way. */
+ *   base and stride allows, the same bits either way.
+ * nkv_advdiff_cstage: one Horner stage of p(dt G), G = L - i omega, on complex fields with a constant
+ *   forcing inside: the step of the rotating-frame time-stepper resolvent (resolvent.ResolventOperator).
+ *   nekStab's resolvent_op (linear_operators.f90:348-431) integrates the real state under cos / sin forcing
+ *   and takes the imaginary part from a quarter-period run; here u = Re[y e^{i omega t}] turns the forcing
+ *   into a constant and the coupling of the halves into -i omega y.  L is the layout of the
+ *   re/im PAIR vectors (n_v even): n = n_v / 2 points per half, the halves given by separate pointers with
+ *   one stride per operand (field f at ptr + f*stride), since in a pair vector the im half starts n doubles
+ *   after the re half, which is 16-byte aligned only for even n.  Per point, in this order, no contraction:
+ *     g_re = (minv r_re + omega s_im) [+ f_re]      g_im = (minv r_im - omega s_re) [+ f_im]
+ *     w_re = v_re + c g_re                          w_im = v_im + c g_im
+ *   s: the stage's source vector, r: the averaged right-hand sides of its halves, minv: n doubles.
+ *   v = NULL (both halves) stands for zero, f = NULL (both halves) for no forcing.  w may be v; the spans of
+ *   w must not meet those of minv, r, s or f, nor each other.  The adjoint stage passes -omega.
+ *   zero_rest != 0 (w a whole pair state vector: nfld = n_wf, w_stride = sv, w_im = w_re + n) also zeroes the
+ *   n_p pressure rows and the time slot; padding rows are never written.  16-byte accesses when every
+ *   pointer and stride allows, the same bits either way. */
 int nkv_advdiff_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
                     const double* ym, const double* zm, const double* U, int64_t U_stride, const double* kappa,
                     const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
@@ -743,6 +759,11 @@ int nkv_advdiff_bm1(const nkv_layout* L, int lx1, int ldim, const double* D, con
 int nkv_advdiff_stage(const nkv_layout* L, const double* v, int64_t v_stride, const double* minv, const double* r,
                       int64_t r_stride, double c, double* w, int64_t w_stride, int nfld, int zero_rest,
                       void* stream);
+int nkv_advdiff_cstage(const nkv_layout* L, const double* v_re, const double* v_im, int64_t v_stride,
+                       const double* minv, const double* r_re, const double* r_im, int64_t r_stride,
+                       const double* s_re, const double* s_im, int64_t s_stride, const double* f_re,
+                       const double* f_im, int64_t f_stride, double omega, double c, double* w_re, double* w_im,
+                       int64_t w_stride, int nfld, int zero_rest, void* stream);
 
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live

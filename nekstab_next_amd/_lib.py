@@ -149,6 +149,8 @@ _SIGNATURES = {
                                 c_int, _P]),
     "nkv_advdiff_bm1": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "nkv_advdiff_stage": (c_int, [_L, _P, c_int64, _P, _P, c_int64, c_double, _P, c_int64, c_int, c_int, _P]),
+    "nkv_advdiff_cstage": (c_int, [_L, _P, _P, c_int64, _P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, c_double,
+                                   c_double, _P, _P, c_int64, c_int, c_int, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

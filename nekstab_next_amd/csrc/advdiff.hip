@@ -213,6 +213,80 @@ __global__ __launch_bounds__(kThreads) void k_advdiff_stage(int64_t n, const dou
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// One Horner stage of p(dt G), G = L - i omega on complex fields kept as re / im halves, with a constant
+// forcing inside (the rotating-frame resolvent of resolvent.py; linear_operators.f90:348-431 integrates the
+// real state under cos / sin forcing instead).  Per point, in this order and without contraction:
+//   g_re = (m r_re + omega s_im) [+ f_re]      g_im = (m r_im - omega s_re) [+ f_im]
+//   w_re = v_re + c g_re                        w_im = v_im + c g_im
+// r: the averaged right-hand sides of the two halves of the stage's source s; v = NULL stands for zero,
+// f = NULL for no forcing.  One thread forms both halves of a point, so w may be v; w is never s, r, f or
+// m (the entry refuses overlapping spans), which is what lets those carry __restrict__.  Nine reads and two
+// writes per point and field in one launch; grid.y = field, the zeroing and VEC as in k_advdiff_stage.
+// ------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_advdiff_cstage(
+    int64_t n, const double* v_re, const double* v_im, int64_t v_stride, const double* __restrict__ m,
+    const double* __restrict__ r_re, const double* __restrict__ r_im, int64_t r_stride,
+    const double* __restrict__ s_re, const double* __restrict__ s_im, int64_t s_stride,
+    const double* __restrict__ f_re, const double* __restrict__ f_im, int64_t f_stride, double omega, double c,
+    double* w_re, double* w_im, int64_t w_stride, double* zero_p, int64_t n_p, double* zero_t) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.y;
+    const double* vr = v_re ? v_re + f * v_stride : nullptr;
+    const double* vi = v_re ? v_im + f * v_stride : nullptr;
+    const double* rr = r_re + f * r_stride;
+    const double* ri = r_im + f * r_stride;
+    const double* sr = s_re + f * s_stride;
+    const double* si = s_im + f * s_stride;
+    const double* fr = f_re ? f_re + f * f_stride : nullptr;
+    const double* fi = f_re ? f_im + f * f_stride : nullptr;
+    double* wr = w_re + f * w_stride;
+    double* wi = w_im + f * w_stride;
+    const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+    auto point = [&](int64_t p) {
+        double gr = m[p] * rr[p] + omega * si[p];
+        double gi = m[p] * ri[p] - omega * sr[p];
+        if (fr) {
+            gr = gr + fr[p];
+            gi = gi + fi[p];
+        }
+        const double tr = c * gr, ti = c * gi;
+        const double o_re = vr ? vr[p] + tr : tr, o_im = vr ? vi[p] + ti : ti;
+        wr[p] = o_re;
+        wi[p] = o_im;
+    };
+    if constexpr (VEC) {
+        const int64_t pairs = n / 2;
+        for (int64_t i = t0; i < pairs; i += step) {
+            const int64_t p = 2 * i;
+            const double2 mm = ld2(m + p), a = ld2(rr + p), b = ld2(ri + p), x = ld2(sr + p), y = ld2(si + p);
+            double2 gr = make_double2(mm.x * a.x + omega * y.x, mm.y * a.y + omega * y.y);
+            double2 gi = make_double2(mm.x * b.x - omega * x.x, mm.y * b.y - omega * x.y);
+            if (fr) {
+                const double2 p_re = ld2(fr + p), p_im = ld2(fi + p);
+                gr = make_double2(gr.x + p_re.x, gr.y + p_re.y);
+                gi = make_double2(gi.x + p_im.x, gi.y + p_im.y);
+            }
+            double2 o_re = make_double2(c * gr.x, c * gr.y), o_im = make_double2(c * gi.x, c * gi.y);
+            if (vr) {
+                const double2 q_re = ld2(vr + p), q_im = ld2(vi + p);
+                o_re = make_double2(q_re.x + o_re.x, q_re.y + o_re.y);
+                o_im = make_double2(q_im.x + o_im.x, q_im.y + o_im.y);
+            }
+            st2(wr + p, o_re);
+            st2(wi + p, o_im);
+        }
+        if ((n & 1) && t0 == 0) point(n - 1);
+    } else {
+        for (int64_t p = t0; p < n; p += step) point(p);
+    }
+    if (f == 0 && zero_p) {
+        for (int64_t p = t0; p < n_p; p += step) zero_p[p] = 0.0;
+        if (t0 == 0) *zero_t = 0.0;
+    }
+}
+
 template <int LDIM, int NX>
 void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
                 const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
@@ -341,6 +415,71 @@ int nkv_advdiff_stage(const nkv_layout* L, const double* v, int64_t v_stride, co
     else
         hipLaunchKernelGGL(k_advdiff_stage<false>, grid, dim3(kThreads), 0, S(stream), n, v, v_stride, minv, r, r_stride,
                            c, w, w_stride, zp, L->n_p, zt);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_advdiff_cstage(const nkv_layout* L, const double* v_re, const double* v_im, int64_t v_stride,
+                       const double* minv, const double* r_re, const double* r_im, int64_t r_stride,
+                       const double* s_re, const double* s_im, int64_t s_stride, const double* f_re,
+                       const double* f_im, int64_t f_stride, double omega, double c, double* w_re, double* w_im,
+                       int64_t w_stride, int nfld, int zero_rest, void* stream) {
+    static const char who[] = "advdiff_cstage";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
+    if (L->n_v % 2) return fail(NKV_EINVAL, "%s: n_v=%lld is odd: L is the layout of re/im pair vectors", who,
+                                (long long)L->n_v);
+    const int64_t n = L->n_v / 2;
+    if (nfld < 1 || nfld > 65535) return fail(NKV_EINVAL, "%s: nfld=%d outside 1..65535", who, nfld);
+    if (!v_re != !v_im) return fail(NKV_EINVAL, "%s: v_re and v_im are both NULL or neither", who);
+    if (!f_re != !f_im) return fail(NKV_EINVAL, "%s: f_re and f_im are both NULL or neither", who);
+    if ((v_re && v_stride < n) || (f_re && f_stride < n) || r_stride < n || s_stride < n || w_stride < n)
+        return fail(NKV_EINVAL,
+                    "%s: strides v_stride=%lld r_stride=%lld s_stride=%lld f_stride=%lld w_stride=%lld below n_v/2=%lld",
+                    who, (long long)v_stride, (long long)r_stride, (long long)s_stride, (long long)f_stride,
+                    (long long)w_stride, (long long)n);
+    CHECK(need(minv, who, "minv"));
+    CHECK(need(r_re, who, "r_re"));
+    CHECK(need(r_im, who, "r_im"));
+    CHECK(need(s_re, who, "s_re"));
+    CHECK(need(s_im, who, "s_im"));
+    CHECK(need(w_re, who, "w_re"));
+    CHECK(need(w_im, who, "w_im"));
+    if (!std::isfinite(c) || !std::isfinite(omega)) return fail(NKV_EINVAL, "%s: c=%g omega=%g", who, c, omega);
+    // w may be v (pointwise) and nothing else: the span of every input half against the span of each half of w
+    auto span = [&](const double* p, int64_t stride) { return p + (int64_t)(nfld - 1) * stride + n; };
+    auto meets_w = [&](const double* p, int64_t stride) {
+        if (!p) return false;
+        const double* e = span(p, stride);
+        return (p < span(w_re, w_stride) && w_re < e) || (p < span(w_im, w_stride) && w_im < e);
+    };
+    if (meets_w(minv, 0) || meets_w(r_re, r_stride) || meets_w(r_im, r_stride) || meets_w(s_re, s_stride) ||
+        meets_w(s_im, s_stride) || meets_w(f_re, f_stride) || meets_w(f_im, f_stride))
+        return fail(NKV_EINVAL, "%s: w overlaps minv, r, s or f (only v may be w)", who);
+    // the halves of w against each other: field i's re against field j's im, d + (j - i) w_stride apart
+    const int64_t d = w_im < w_re ? w_re - w_im : w_im - w_re, k = d / w_stride, rem = d % w_stride;
+    if (d < n || (rem < n && k >= 1 && k <= nfld - 1) || (w_stride - rem < n && k + 1 <= nfld - 1))
+        return fail(NKV_EINVAL, "%s: the halves of w overlap", who);
+    if (zero_rest && (nfld != L->n_wf || w_stride != L->sv || w_im != w_re + n))
+        return fail(NKV_EINVAL,
+                    "%s: zero_rest needs w to be a pair state vector (nfld=%d, n_wf=%d, w_stride=%lld, sv=%lld, "
+                    "w_im = w_re + n_v/2)", who, nfld, L->n_wf, (long long)w_stride, (long long)L->sv);
+    auto a16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const bool vec = n >= 2 && a16(minv) && a16(r_re) && a16(r_im) && a16(s_re) && a16(s_im) && a16(w_re) && a16(w_im) &&
+                     r_stride % 2 == 0 && s_stride % 2 == 0 && w_stride % 2 == 0 &&
+                     (!v_re || (a16(v_re) && a16(v_im) && v_stride % 2 == 0)) &&
+                     (!f_re || (a16(f_re) && a16(f_im) && f_stride % 2 == 0));
+    double* zp = zero_rest ? w_re + (int64_t)L->n_wf * L->sv : nullptr;
+    double* zt = zero_rest ? w_re + rows_of(L) : nullptr;
+    const dim3 grid(grid_for(vec ? n / 2 : n, 1024), nfld);
+    if (vec)
+        hipLaunchKernelGGL(k_advdiff_cstage<true>, grid, dim3(kThreads), 0, S(stream), n, v_re, v_im, v_stride, minv, r_re,
+                           r_im, r_stride, s_re, s_im, s_stride, f_re, f_im, f_stride, omega, c, w_re, w_im, w_stride, zp,
+                           L->n_p, zt);
+    else
+        hipLaunchKernelGGL(k_advdiff_cstage<false>, grid, dim3(kThreads), 0, S(stream), n, v_re, v_im, v_stride, minv, r_re,
+                           r_im, r_stride, s_re, s_im, s_stride, f_re, f_im, f_stride, omega, c, w_re, w_im, w_stride, zp,
+                           L->n_p, zt);
     NKV_LAUNCHED();
     return NKV_OK;
 }

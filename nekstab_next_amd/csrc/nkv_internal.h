@@ -29,7 +29,8 @@
 //   gs.hip            sharded gather-scatter: pack of the shared points, direct-stiffness average of many
 //                     field segments per launch from local points and the values other ranks sent
 //   advdiff.hip       spectral-element advection-diffusion of the dotted fields by a frozen base flow: fused
-//                     weak-form right-hand side (forward and adjoint), mass matrix, Horner stage / projector halves
+//                     weak-form right-hand side (forward and adjoint), mass matrix, Horner stage / projector halves,
+//                     complex Horner stage of the rotating-frame resolvent (re / im halves, forcing inside)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -11,8 +11,9 @@ The operator is any :class:`~nekstab_next_amd.operators.LinearOperator` (the exp
 propagator of a Nek5000 run in production; synthetic operators in the tests) with the sampling
 time ``t`` (``exponential_prop%t``).
 * :func:`resolvent_analysis` — svds of a resolvent operator on complex (re/im pair) vectors,
-  sigma <- sigma**2, ``Spectrum_Sr.dat``.  The resolvent's body (forced Nek5000 run + inner GMRES
-  on Id - A^T) is the caller's operator.
+  sigma <- sigma**2, ``Spectrum_Sr.dat``.  The resolvent's body (forced run + inner GMRES on
+  Id - Phi) is the operator's: :class:`~nekstab_next_amd.resolvent.ResolventOperator` over the model
+  propagator, or the caller's over a Nek5000 run.
 """
 from __future__ import annotations
 
@@ -99,8 +100,9 @@ def resolvent_analysis(ctx: NekContext, R: LinearOperator, seed: NekVector, k_di
     re/im pair vectors, so the cmplx dot re.re + im.im is the layout's weighted dot and svds runs
     unchanged); ``R`` maps complex to complex (``matvec``) with its adjoint (``rmatvec``).  In
     nekStab R's body is a forced Nek5000 integration plus an inner GMRES
-    (linear_operators.f90:348-431) — any operator with that interface plugs in;
-    :class:`~nekstab_next_amd.operators.ComplexDiagOperator` is the synthetic, exactly known one.
+    (linear_operators.f90:348-431) — any operator with that interface plugs in:
+    :class:`~nekstab_next_amd.resolvent.ResolventOperator` is that body over the model propagator,
+    :class:`~nekstab_next_amd.operators.ComplexDiagOperator` the synthetic, exactly known one.
     The reference seeds re and im separately (prepare_seed on U%re, U%im, :147-148); here the
     seed pair is normalised as one vector (the bidiagonalisation only needs its direction).  The
     cmplx dot is real, so x and i x are independent directions and every singular value of the

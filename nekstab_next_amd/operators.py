@@ -231,8 +231,9 @@ class ComplexDiagOperator(LinearOperator):
     """y = C x, C complex diagonal, on complex vectors stored as re/im pair vectors
     (:class:`~nekstab_next_amd.layout.PairLayout`); ``rmatvec`` applies conj(C) — the adjoint under
     the cmplx dot re.re + im.im.  ``cr``/``ci`` are padded pair-layout vectors read at the re rows
-    (:func:`~nekstab_next_amd.synthetic.resolvent_diag`).  The synthetic stand-in for nekStab's
-    ``resolvent_op`` (core/linear_operators.f90:309-431), whose body is a forced Nek5000 run."""
+    (:func:`~nekstab_next_amd.synthetic.resolvent_diag`).  The synthetic, exactly known counterpart of
+    nekStab's ``resolvent_op`` (core/linear_operators.f90:309-431); its body as a time stepper on the GLL mesh
+    (forced integration + inner GMRES on ``I - Phi``) is :class:`~nekstab_next_amd.resolvent.ResolventOperator`."""
 
     def __init__(self, ctx: NekContext, cr, ci):
         from .layout import PairLayout
