@@ -765,6 +765,44 @@ int nkv_advdiff_cstage(const nkv_layout* L, const double* v_re, const double* v_
                        const double* f_im, int64_t f_stride, double omega, double c, double* w_re, double* w_im,
                        int64_t w_stride, int nfld, int zero_rest, void* stream);
 
+/* ---- pressure-free viscous Burgers flow: its linearisation, its adjoint and the RK4 stage ------------
+ * The nonlinear flow nekStab's Newton-then-stability workflow needs on one mesh (fixed point at
+ * uparam(1)=2, stability at 3, adjoint at 3.2; newton_linearized_map, matvec.f90:520-571): the velocity
+ * advects itself and every scalar; pressure and incompressibility stay Nek5000's.  Conventions, arithmetic
+ * and the treatment of bad arguments and empty shards: as for the advection-diffusion entries above.
+ *
+ * nkv_linconv_rhs: the LOCAL right-hand side of the convection linearised about a base state B of nfld
+ *   fields (field f at B + f*B_stride; its first ldim fields are the advecting velocity), for all nfld
+ *   fields of u in one tiled pass.  With r_advdiff(u; U) the two forms of nkv_advdiff_rhs:
+ *     forward:  r_f = r_advdiff,f(u; U = B_vel)     - bm1 sum_{d<ldim} u_d d_d B_f
+ *     adjoint:  r_f = r_advdiff,adj,f(u; U = B_vel) - [f < ldim] bm1 sum_{f'<nfld} u_f' d_f B_f'
+ *   d_d B_f as nkv_gradm1 forms it (element-local), from B_f staged in one more LDS tile: grad B is never
+ *   written to global memory.  The sums run in ascending index; the advection-diffusion part keeps the
+ *   operand order of nkv_advdiff_rhs.  The two are transposes of each other as matrices on the local points,
+ *   so minv dsavg(r_adj) is the exact adjoint of minv dsavg(r_fwd) in the bm1 inner product.  LDS:
+ *   lx1^2 + (ldim + 2) nt doubles, 40,800 bytes at lx1 = 10 in 3-D.  nfld >= ldim; the span of r must not
+ *   meet those of u or B.  The nonlinear right-hand side needs no entry of its own: it is the forward
+ *   nkv_advdiff_rhs with U = u (both read-only there).
+ * nkv_rk4_stage: one stage of classical RK4 for nfld fields in one launch (field f at ptr + f*stride).  Per
+ *   point, in this order:
+ *     k = minv r [+ g]      w = v + a k      acc' = (first ? v : acc) + b k
+ *   r: the averaged right-hand side of the stage's state, g: a constant forcing (NULL: none), w: the next
+ *   stage's state (NULL on the last stage), acc' written to acc_out, which may be acc or v itself; no other
+ *   operand may meet w or acc_out.  v = NULL stands for zero (with first != 0, w = NULL and b = 1:
+ *   acc_out = k, the generator itself); otherwise v is read when first != 0 or w is given, acc when
+ *   first == 0.
+ *   zero_rest != 0 (acc_out a whole state vector: nfld = n_wf, ao_stride = sv) also zeroes the n_p pressure
+ *   rows and the time slot; padding rows are never written.  16-byte accesses when every base and stride
+ *   allows, the same bits either way. */
+int nkv_linconv_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                    const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
+                    void* stream);
+int nkv_rk4_stage(const nkv_layout* L, const double* v, int64_t v_stride, const double* minv, const double* r,
+                  int64_t r_stride, const double* g, int64_t g_stride, double a, double b, int first,
+                  const double* acc, int64_t acc_stride, double* w, int64_t w_stride, double* acc_out,
+                  int64_t ao_stride, int nfld, int zero_rest, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

@@ -16,7 +16,8 @@ def __getattr__(name):
 
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
                 "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
-                "postproc", "vortex", "forcing", "monitors", "gs", "advdiff", "resolvent", "_lib"):
+                "postproc", "vortex", "forcing", "monitors", "gs", "advdiff", "resolvent", "burgers",
+                "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
     if name in ("SFD", "TDF"):   # the fixed-point forcing classes (fixedp.py)
@@ -29,4 +30,6 @@ def __getattr__(name):
         return getattr(importlib.import_module(".advdiff", __name__), name)
     if name in ("ResolventOperator", "pair_context"):   # the time-stepper resolvent over it (resolvent.py)
         return getattr(importlib.import_module(".resolvent", __name__), name)
+    if name in ("LinearisedConvection", "ViscousBurgers"):   # the nonlinear flow and its linearisation (burgers.py)
+        return getattr(importlib.import_module(".burgers", __name__), name)
     raise AttributeError(name)

@@ -9,6 +9,9 @@
 // reference direction a.  r is the LOCAL (unassembled) right-hand side: dssum and the inverse mass matrix
 // follow as dsavg and the pointwise k_advdiff_stage.  No contraction; element-local, so it shards with the
 // elements and any element sub-range gives the bits of the whole.
+// Further down: the same right-hand side with the production term of a base state B of all fields
+// (k_linconv_rhs: the linearisation of the viscous Burgers flow of burgers.py and its adjoint) and the
+// classical RK4 stage of that flow (k_rk4_stage); its nonlinear right-hand side is k_advdiff_rhs with U = u.
 #include "nkv_internal.h"
 
 namespace {
@@ -287,6 +290,220 @@ __global__ __launch_bounds__(kThreads) void k_advdiff_cstage(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The linearised convection about a base state B of n_wf fields (velocity first): k_advdiff_rhs with the
+// advecting velocity B_0..B_{LDIM-1} plus the production term, for all fields in one launch.
+//   forward:  r_f = r_advdiff,f(u; U = B_vel) - bm1 sum_{d<LDIM} u_d d_d B_f
+//   adjoint:  r_f = r_advdiff,adj,f(u; U = B_vel) - [f < LDIM] bm1 sum_{f'<nfld} u_f' d_f B_f'
+// d_d B_f as k_gradm1 forms it, from B_f staged in one more tile (Bt) and the same line sums: grad B never
+// touches global memory.  The sums run in ascending index; the advection-diffusion part keeps the operand
+// order of k_advdiff_rhs.
+// Forward: B_f is staged next to u_f, no barrier more than k_advdiff_rhs.  Adjoint: velocity component d
+// closes with sum_f' u_f' d_d B_f', so a first sweep over the base fields accumulates LDIM registers; it
+// alternates between the two field tiles, one barrier per base field.  LDS: lx1^2 + (LDIM + 2) nt doubles,
+// 40,800 bytes at lx1 = 10 in 3-D.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX, bool ADJ>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_linconv_rhs(
+    int64_t nel, int epb, int nfld, const double* __restrict__ Dg, const double* __restrict__ wg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ B, int64_t b_stride, const double* __restrict__ kappa, const double* __restrict__ u,
+    int64_t u_stride, double* __restrict__ r, int64_t r_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    const int nt = epb * pts;
+    double* D = lds;                         // D(i, m) at D[i*NX + m]
+    double* X = D + NX * NX;                 // coordinates, then the flux along r
+    double* Y = X + nt;                      // ... along s
+    double* Z = Y + nt;                      // ... along t (3-D only)
+    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated
+    double* Bt = U + nt;                     // the base field being differentiated
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const PointIndex<LDIM, NX> ix(tid);
+    const double wt = ix.weight(wg);
+    const int le = tid / pts;
+    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = D + ix.j;
+    const double* Dck = D + ix.k;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double jacmi = 1.0 / jac;
+        const double bm = jac * wt;
+        double Ub[LDIM];       // the advecting velocity B_d
+        double P[LDIM];        // forward: the velocity perturbation u_d; adjoint: sum_f' u_f' d_d B_f'
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) {
+            Ub[d] = live ? B[d * b_stride + p] : 0.0;
+            P[d] = (!ADJ && live) ? u[d * u_stride + p] : 0.0;
+        }
+        if constexpr (ADJ) {
+            for (int f = 0; f < nfld; ++f) {
+                double* T = (f & 1) ? Bt : U;   // the tile written two fields ago: a barrier lies between
+                if (live) T[tid] = B[f * b_stride + p];
+                __syncthreads();
+                if (live) {
+                    double br, bs, bt;
+                    line_sums<LDIM, NX>(q, T, br, bs, bt);
+                    const double uf = u[f * u_stride + p];
+#pragma unroll
+                    for (int d = 0; d < LDIM; ++d) {
+                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                        P[d] = f == 0 ? uf * db : P[d] + uf * db;
+                    }
+                }
+            }
+        }
+        for (int f = 0; f < nfld; ++f) {
+            if (f > 0 || ADJ) __syncthreads();   // every lane is done reading the previous field and its fluxes
+            if (live) {
+                U[tid] = u[f * u_stride + p];
+                if constexpr (!ADJ) Bt[tid] = B[f * b_stride + p];
+            }
+            __syncthreads();              // (and every lane has formed its factors: the tiles are free)
+            double adv = 0.0, prod = 0.0;
+            if (live) {
+                double ur, us, ut;
+                line_sums<LDIM, NX>(q, U, ur, us, ut);
+                const double kb = -kappa[f] * bm;
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
+                    if constexpr (ADJ) {
+                        G[d] = kb * du - bm * Ub[d] * U[tid];
+                    } else {
+                        G[d] = kb * du;
+                        adv = adv + Ub[d] * du;
+                    }
+                }
+                if constexpr (!ADJ) {
+                    double br, bs, bt;
+                    line_sums<LDIM, NX>(q, Bt, br, bs, bt);
+                    prod = P[0] * physical_derivative<LDIM>(g, jacmi, 0, br, bs, bt);
+#pragma unroll
+                    for (int d = 1; d < LDIM; ++d)
+                        prod = prod + P[d] * physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                } else {
+#pragma unroll
+                    for (int d = 0; d < LDIM; ++d)
+                        if (f == d) prod = P[d];
+                }
+                double* tiles[3] = {X, Y, Z};
+#pragma unroll
+                for (int a = 0; a < LDIM; ++a) {
+                    double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+                    tiles[a][tid] = F;
+                }
+            }
+            __syncthreads();
+            if (live) {
+                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+                for (int m = 1; m < NX; ++m) {
+                    tr = tr + Dci[m * NX] * X[q.ri + m];
+                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+                }
+                double acc = tr + ts;
+                if constexpr (LDIM == 3) {
+                    double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+                    acc = acc + tt;
+                }
+                if constexpr (ADJ)
+                    r[f * r_stride + p] = f < LDIM ? acc - bm * prod : acc;
+                else
+                    r[f * r_stride + p] = (acc - bm * adv) - bm * prod;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// One stage of classical RK4 for all fields (grid.y = field).  Per point, in this order, no contraction:
+//   k = m r [+ g]      w = v + a k      acc' = (first ? v : acc) + b k
+// m: the pointwise inverse assembled mass matrix, r: the averaged right-hand side of the stage's state,
+// g: a constant forcing.  v = NULL stands for zero, as in k_advdiff_stage.  w (the next stage's state) may be
+// NULL; acc' goes to ao, which may be acc or v (one thread reads a point's operands before it writes them).
+// The zeroing of the rest of a state vector and VEC as in k_advdiff_stage.
+// ------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_rk4_stage(int64_t n, const double* v, int64_t v_stride,
+                                                        const double* __restrict__ m, const double* __restrict__ r,
+                                                        int64_t r_stride, const double* __restrict__ g,
+                                                        int64_t g_stride, double a, double b, int first,
+                                                        const double* acc, int64_t acc_stride, double* w,
+                                                        int64_t w_stride, double* ao, int64_t ao_stride, double* zero_p,
+                                                        int64_t n_p, double* zero_t) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.y;
+    const double* vf = v ? v + f * v_stride : nullptr;
+    const double* rf = r + f * r_stride;
+    const double* gf = g ? g + f * g_stride : nullptr;
+    const double* af = first ? vf : acc + f * acc_stride;
+    double* wf = w ? w + f * w_stride : nullptr;
+    double* of = ao + f * ao_stride;
+    const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+    auto point = [&](int64_t p) {
+        double k = m[p] * rf[p];
+        if (gf) k = k + gf[p];
+        const double s = a * k, t = b * k;
+        const double base = af ? af[p] : 0.0;
+        if (wf) wf[p] = vf ? vf[p] + s : s;
+        of[p] = af ? base + t : t;
+    };
+    if constexpr (VEC) {
+        const int64_t pairs = n / 2;
+        for (int64_t i = t0; i < pairs; i += step) {
+            const int64_t p = 2 * i;
+            const double2 mm = ld2(m + p), rr = ld2(rf + p);
+            double2 k = make_double2(mm.x * rr.x, mm.y * rr.y);
+            if (gf) {
+                const double2 gg = ld2(gf + p);
+                k = make_double2(k.x + gg.x, k.y + gg.y);
+            }
+            const double2 t = make_double2(b * k.x, b * k.y);
+            double2 o = t;
+            if (af) {   // (read before w is written: acc_out may be v)
+                const double2 base = ld2(af + p);
+                o = make_double2(base.x + t.x, base.y + t.y);
+            }
+            if (wf) {
+                double2 s = make_double2(a * k.x, a * k.y);
+                if (vf) {
+                    const double2 vv = ld2(vf + p);
+                    s = make_double2(vv.x + s.x, vv.y + s.y);
+                }
+                st2(wf + p, s);
+            }
+            st2(of + p, o);
+        }
+        if ((n & 1) && t0 == 0) point(n - 1);
+    } else {
+        for (int64_t p = t0; p < n; p += step) point(p);
+    }
+    if (f == 0 && zero_p) {
+        for (int64_t p = t0; p < n_p; p += step) zero_p[p] = 0.0;
+        if (t0 == 0) *zero_t = 0.0;
+    }
+}
+
 template <int LDIM, int NX>
 void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
                 const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
@@ -315,6 +532,24 @@ void launch_bm1(int64_t nel, const double* D, const double* w, const double* xm,
     const int grid = (int)std::min<int64_t>(groups, 16384);
     hipLaunchKernelGGL((k_advdiff_bm1<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, w, xm,
                        ym, zm, bm1);
+}
+
+template <int LDIM, int NX>
+void launch_linconv(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
+                    const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u,
+                    int64_t u_stride, double* r, int64_t r_stride, int adjoint, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);
+    static_assert(sizeof(double) * (10 * 10 + 5 * 1000) <= 65536, "dynamic LDS within 64 KiB at lx1 = 10");
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    if (adjoint)
+        hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
+                           nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
+    else
+        hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
+                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
 }
 
 }  // namespace
@@ -480,6 +715,109 @@ int nkv_advdiff_cstage(const nkv_layout* L, const double* v_re, const double* v_
         hipLaunchKernelGGL(k_advdiff_cstage<false>, grid, dim3(kThreads), 0, S(stream), n, v_re, v_im, v_stride, minv, r_re,
                            r_im, r_stride, s_re, s_im, s_stride, f_re, f_im, f_stride, omega, c, w_re, w_im, w_stride, zp,
                            L->n_p, zt);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_linconv_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                    const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                    const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
+                    void* stream) {
+    static const char who[] = "linconv_rhs";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
+                                 nfld, ldim);
+    if (B_stride < L->n_v || u_stride < L->n_v || r_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: strides B_stride=%lld u_stride=%lld r_stride=%lld below n_v=%lld", who,
+                    (long long)B_stride, (long long)u_stride, (long long)r_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(B, who, "B"));
+    CHECK(need(kappa, who, "kappa"));
+    CHECK(need(u, who, "u"));
+    CHECK(need(r, who, "r"));
+    // r is written field by field while later fields of u and B are still to be read: no overlap of the spans
+    auto meets_r = [&](const double* p, int64_t stride) {
+        const double* e = p + (int64_t)(nfld - 1) * stride + L->n_v;
+        const double* re = r + (int64_t)(nfld - 1) * r_stride + L->n_v;
+        return p < re && r < e;
+    };
+    if (meets_r(u, u_stride) || meets_r(B, B_stride)) return fail(NKV_EINVAL, "%s: r overlaps u or B", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_LC_RHS(NX)                                                                                                \
+    case NX:                                                                                                          \
+        if (ldim == 3)                                                                                                \
+            launch_linconv<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r, r_stride, adjoint, \
+                                  st);                                                                                \
+        else                                                                                                          \
+            launch_linconv<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r, r_stride, adjoint, \
+                                  st);                                                                                \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_LC_RHS) }
+#undef NKV_LC_RHS
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_rk4_stage(const nkv_layout* L, const double* v, int64_t v_stride, const double* minv, const double* r,
+                  int64_t r_stride, const double* g, int64_t g_stride, double a, double b, int first,
+                  const double* acc, int64_t acc_stride, double* w, int64_t w_stride, double* acc_out,
+                  int64_t ao_stride, int nfld, int zero_rest, void* stream) {
+    static const char who[] = "rk4_stage";
+    CHECK(check_layout(L));
+    const int64_t n = L->n_v;
+    if (n == 0) return NKV_OK;   // an empty shard: nothing to touch
+    if (nfld < 1 || nfld > 65535) return fail(NKV_EINVAL, "%s: nfld=%d outside 1..65535", who, nfld);
+    const bool need_v = (first || w) && v, need_acc = !first;   // v = NULL stands for zero
+    if ((need_v && v_stride < n) || r_stride < n || (g && g_stride < n) || (need_acc && acc_stride < n) ||
+        (w && w_stride < n) || ao_stride < n)
+        return fail(NKV_EINVAL,
+                    "%s: strides v_stride=%lld r_stride=%lld g_stride=%lld acc_stride=%lld w_stride=%lld "
+                    "ao_stride=%lld below n_v=%lld", who, (long long)v_stride, (long long)r_stride, (long long)g_stride,
+                    (long long)acc_stride, (long long)w_stride, (long long)ao_stride, (long long)n);
+    CHECK(need(minv, who, "minv"));
+    CHECK(need(r, who, "r"));
+    CHECK(need(acc_out, who, "acc_out"));
+    if (need_acc) CHECK(need(acc, who, "acc"));
+    if (!std::isfinite(a) || !std::isfinite(b)) return fail(NKV_EINVAL, "%s: a=%g b=%g", who, a, b);
+    // acc_out may be acc or v exactly (pointwise); otherwise no output span meets another operand's
+    auto end = [&](const double* p, int64_t stride) { return p + (int64_t)(nfld - 1) * stride + n; };
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        return p && o && p < end(o, os) && o < end(p, ps);
+    };
+    const double* vv = need_v ? v : nullptr;
+    const double* aa = need_acc ? acc : nullptr;
+    auto out_bad = [&](const double* o, int64_t os, bool may_alias) {
+        if (meets(minv, 0, o, os) || meets(r, r_stride, o, os) || meets(g, g_stride, o, os)) return true;
+        if (meets(vv, v_stride, o, os) && !(may_alias && vv == o && v_stride == os)) return true;
+        if (meets(aa, acc_stride, o, os) && !(may_alias && aa == o && acc_stride == os)) return true;
+        return false;
+    };
+    if (out_bad(acc_out, ao_stride, true) || (w && (out_bad(w, w_stride, false) || meets(w, w_stride, acc_out, ao_stride))))
+        return fail(NKV_EINVAL, "%s: w or acc_out overlaps an operand (only acc_out may be acc or v)", who);
+    if (zero_rest && (nfld != L->n_wf || ao_stride != L->sv))
+        return fail(NKV_EINVAL,
+                    "%s: zero_rest needs acc_out to be a state vector (nfld=%d, n_wf=%d, ao_stride=%lld, sv=%lld)", who,
+                    nfld, L->n_wf, (long long)ao_stride, (long long)L->sv);
+    auto a16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const bool vec = n >= 2 && a16(minv) && a16(r) && r_stride % 2 == 0 && a16(acc_out) && ao_stride % 2 == 0 &&
+                     (!need_v || (a16(v) && v_stride % 2 == 0)) && (!g || (a16(g) && g_stride % 2 == 0)) &&
+                     (!need_acc || (a16(acc) && acc_stride % 2 == 0)) && (!w || (a16(w) && w_stride % 2 == 0));
+    double* zp = zero_rest ? acc_out + (int64_t)L->n_wf * L->sv : nullptr;
+    double* zt = zero_rest ? acc_out + rows_of(L) : nullptr;
+    const dim3 grid(grid_for(vec ? n / 2 : n, 1024), nfld);
+    if (vec)
+        hipLaunchKernelGGL(k_rk4_stage<true>, grid, dim3(kThreads), 0, S(stream), n, vv, v_stride, minv, r, r_stride, g,
+                           g_stride, a, b, first ? 1 : 0, aa, acc_stride, w, w_stride, acc_out, ao_stride, zp, L->n_p, zt);
+    else
+        hipLaunchKernelGGL(k_rk4_stage<false>, grid, dim3(kThreads), 0, S(stream), n, vv, v_stride, minv, r, r_stride, g,
+                           g_stride, a, b, first ? 1 : 0, aa, acc_stride, w, w_stride, acc_out, ao_stride, zp, L->n_p, zt);
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -30,7 +30,9 @@
 //                     field segments per launch from local points and the values other ranks sent
 //   advdiff.hip       spectral-element advection-diffusion of the dotted fields by a frozen base flow: fused
 //                     weak-form right-hand side (forward and adjoint), mass matrix, Horner stage / projector halves,
-//                     complex Horner stage of the rotating-frame resolvent (re / im halves, forcing inside)
+//                     complex Horner stage of the rotating-frame resolvent (re / im halves, forcing inside);
+//                     the convection linearised about a base state (production term, forward and adjoint) and
+//                     the classical RK4 stage of the viscous Burgers flow
 #pragma once
 
 #include <hip/hip_runtime.h>

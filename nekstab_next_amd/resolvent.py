@@ -78,6 +78,12 @@ class ResolventOperator(LinearOperator):
 
     def __init__(self, pctx: NekContext, adv: AdvectionDiffusion, omega: float, tol: float = 1e-10, kdim: int = 60,
                  maxiter: int = 20):
+        from .burgers import LinearisedConvection
+
+        if isinstance(adv, LinearisedConvection):
+            raise ValueError("ResolventOperator: a LinearisedConvection is refused: the resolvent steps with "
+                             "nkv_advdiff_rhs and would silently drop the production term (u'.grad)B; a coupled "
+                             "resolvent is not implemented (DESIGN §10)")
         base = adv.ctx.layout
         if not isinstance(pctx.layout, PairLayout) or pctx.layout != pair_layout(base):
             raise ValueError("ResolventOperator: pctx must be a context on pair_layout(adv.ctx.layout)")
