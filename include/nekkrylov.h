@@ -369,6 +369,22 @@ int nkv_rotate(const nkv_layout* L, double* Q, int k, const double* V_dev, int l
 int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, int ldv, int n_out,
                     void* stream);
 
+/* The kernel nkv_rotate_cols launches for (L, k, ldv, n_out).  Host only: no device work, callable
+ * without a GPU.  nkv_rotate_cols decides through this function, so the two never disagree.
+ *   path          : NKV_ROT_PATH_FEW (VALU streaming, <= 16 kept columns), _WIDE (f64 MFMA, 16-byte loads, V
+ *                   whole in LDS, 32-bit lane offsets: only while (3 ld + 30) * 8 < 2^32), _STREAM (f64 MFMA,
+ *                   V whole in LDS, 64-bit offsets) or _CHUNKED (V through LDS in k-chunks)
+ *   inst          : that kernel's template parameter: the kept columns (FEW) or its 16-column blocks
+ *   wg_threads    : threads per workgroup of the launch
+ *   rows_per_tile : rows one workgroup rotates per trip of its persistent loop
+ * The status of a bad layout, k, ldv or n_out is nkv_rotate_cols's; a NULL output is NKV_EINVAL. */
+#define NKV_ROT_PATH_FEW 1
+#define NKV_ROT_PATH_WIDE 2
+#define NKV_ROT_PATH_STREAM 3
+#define NKV_ROT_PATH_CHUNKED 4
+int nkv_rotate_plan(const nkv_layout* L, int k, int ldv, int n_out, int* path, int* inst, int* wg_threads,
+                    int* rows_per_tile);
+
 /* ---- synthetic operators (the matvec boundary, linear_operators.f90:17-23) ----------------
  * op_diag: y = d .* x over every stored row; y.time = time_scale * x.time.
  * op_rot2: per weighted point i, (u,v) = (wf_0[i], wf_1[i]):

@@ -22,6 +22,8 @@ NKV_TILE = 4096
 NKV_MAX_COLS = 1024   # most columns per multi-dot (include/nekkrylov.h)
 NKV_ROT_MAX_OUT = 256   # most output columns of a basis rotation with more than 16 kept (include/nekkrylov.h)
 NKV_GS_MAX_FIELDS = 64   # most field segments per gather-scatter launch (include/nekkrylov.h)
+# the kernel family nkv_rotate_plan reports (include/nekkrylov.h)
+NKV_ROT_PATH_FEW, NKV_ROT_PATH_WIDE, NKV_ROT_PATH_STREAM, NKV_ROT_PATH_CHUNKED = 1, 2, 3, 4
 NKV_OK, NKV_EINVAL, NKV_EHIP, NKV_ENAN, NKV_ESHAPE, NKV_ECALLBACK, NKV_EBREAKDOWN = 0, 1, 2, 3, 4, 5, 6
 NKV_TIME = 0x1
 NKV_ACCUMULATE = 0x2
@@ -114,6 +116,8 @@ _SIGNATURES = {
     "nkv_axpy_dot": (c_int, [_L, _P, _P, _P, _P, _P, _P, _P, c_uint, _P]),
     "nkv_rotate": (c_int, [_L, _P, c_int, _P, c_int, _P]),
     "nkv_rotate_cols": (c_int, [_L, _P, c_int, _P, c_int, c_int, _P]),
+    "nkv_rotate_plan": (c_int, [_L, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                POINTER(c_int)]),
     "nkv_op_diag": (c_int, [_L, _P, _P, _P, c_double, _P]),
     "nkv_op_rot2": (c_int, [_L, _P, _P, _P, _P, _P, c_int, _P]),
     "nkv_op_cdiag": (c_int, [_L, _P, _P, _P, _P, c_int, _P]),

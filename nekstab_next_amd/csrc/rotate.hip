@@ -174,7 +174,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_rotate_wide(double* __restrict__
     const double* vs = Vs + lk * cp + lr;
     const int kl = k - 1, nf = k / (4 * U);   // nf: batches whose k-rows are all < k
     // a lane's byte offset from its wave's (uniform) row base: SGPR base + 32-bit VGPR offset per
-    // load, with no per-lane 64-bit address arithmetic (lk * ld * 8 < 4 GB: ld < 2^27 doubles)
+    // load, with no per-lane 64-bit address arithmetic.  The largest one, (3 ld + 30) * 8 at lk = 3,
+    // lr = 15, must fit 32 bits: nkv_rotate_plan chooses this kernel only for ld <= kRotWideMaxLd
+    // (178,956,960 doubles) and sends longer vectors to the 64-bit kernels below
     const uint32_t lane_off = (uint32_t)(((int64_t)lk * ld + 2 * lr) * (int64_t)sizeof(double));
     typedef double2 Batch[U];
     int64_t tile = t_lo + blockIdx.x;   // this launch's row band: tiles [t_lo, t_hi)
@@ -461,22 +463,40 @@ __global__ __launch_bounds__(kThreads) void k_rotate_few(double* __restrict__ Q,
 #endif
 static_assert(NKV_TILE % (4 * 16) == 0 && NKV_TILE % (8 * 16) == 0, "a 16-row slab per wave must tile the padding");
 
+// ---- launch shapes: what nkv_rotate_plan reports is what the launchers below use ----------------
+constexpr size_t kRotLdsMax = 160 * 1024;   // LDS of one CU: V[:, 0:n_out] must fit it whole (wide, stream)
+// waves per workgroup of the streaming rotation (the register budget: launch_rotate_stream)
+constexpr int rot_stream_waves(int mb) { return mb <= 3 ? NKV_ROT_WAVES : NKV_ROT_WAVES / 2; }
+// ... and its LDS: Vs[c * kp + i], kp = 2 (mod 32) doubles
+inline int rot_stream_kp(int k) { return ((k + 31) & ~31) + 2; }
+inline size_t rot_stream_lds(int nact, int k) { return (size_t)nact * 16 * rot_stream_kp(k) * sizeof(double); }
+// past NKV_ROT_CHUNK_W8_MAX 16-column blocks the 4 x MB accumulators of the chunked rotation need one
+// wave per SIMD (512 registers)
+constexpr int rot_chunked_waves(int mb) { return mb > NKV_ROT_CHUNK_W8_MAX ? 4 : 8; }
+// row pairs per thread of the few-column rotation (launch_rotate_few)
+constexpr int rot_few_pairs(int no) { return no <= 8 ? NKV_ROTF_P : 2; }
+// rows one workgroup rotates per trip: a 16-row slab per wave (x NKV_ROT_NB in the streaming form), two
+// rows per thread and row pair in the few-column form
+constexpr int rot_stream_rows(int mb) { return rot_stream_waves(mb) * NKV_ROT_NB * 16; }
+constexpr int rot_chunked_rows(int mb) { return rot_chunked_waves(mb) * 16; }
+constexpr int rot_few_rows(int no) { return kThreads * rot_few_pairs(no) * 2; }
+
 template <int MB>
-int launch_rotate_stream(const nkv_layout* L, double* Q, int k, const double* V, int ldv, int n_out,
-                                int kp, size_t lds, void* stream) {
+int launch_rotate_stream(const nkv_layout* L, double* Q, int k, const double* V, int ldv, int n_out, void* stream) {
     // register budget (gfx950, U = 4, measured with -Rpass-analysis=kernel-resource-usage in round 6):
     // MB = 1/2/3 at 16 waves per workgroup 52/74/96 VGPRs; MB = 4..8 at 8 waves 118/146/168/235/245 (the
     // three-batch path from MB = 5), no spills; 16 waves/WG allow 128 per lane, so wide column blocks run
     // with half the waves (256 VGPRs)
-    constexpr int NB = NKV_ROT_NB, W = MB <= 3 ? NKV_ROT_WAVES : NKV_ROT_WAVES / 2, U = NKV_ROT_U;
+    constexpr int NB = NKV_ROT_NB, W = rot_stream_waves(MB), U = NKV_ROT_U;
     auto kern = k_rotate_stream<NB, MB, W, U>;
+    const int kp = rot_stream_kp(k);
+    const size_t lds = rot_stream_lds(MB, k);
     static bool attr_set = false;
     if (!attr_set) {
-        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRotLdsMax));
         attr_set = true;
     }
-    const int64_t rows_tile = (int64_t)W * NB * 16;
-    const int64_t n_tiles = rows_of(L) / rows_tile;
+    const int64_t n_tiles = rows_of(L) / rot_stream_rows(MB);
     if (n_tiles < 1) return NKV_OK;
     int per_cu = (int)((160 * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 32 / W ? 32 / W : per_cu);   // LDS and 32 waves per CU
@@ -505,23 +525,31 @@ int launch_rotate_stream(const nkv_layout* L, double* Q, int k, const double* V,
                             // lose here: 2 rounds -10 %, 8 rounds -2 %, profiles/r06d_tune_rotw_bands.log)
 #endif
 static_assert(NKV_TILE % (NKV_ROTW_W * 32) == 0, "a 32-row slab per wave must tile the padding");
+constexpr int kRotWideRows = NKV_ROTW_W * 32;   // rows one workgroup of the wide-load rotation rotates per trip
 
 // LDS of the wide-load rotation: V k-major, kpad rows of cp doubles (cp = 16 mod 32)
 inline int rotw_cp(int nact) { return ((16 * nact + 31) / 32) * 32 + 16; }
 inline int rotw_kpad(int k) { return ((k + 4 * NKV_ROTW_U - 1) / (4 * NKV_ROTW_U)) * 4 * NKV_ROTW_U; }
+inline size_t rotw_lds(int nact, int k) { return (size_t)rotw_kpad(k) * rotw_cp(nact) * sizeof(double); }
+// k_rotate_wide keeps a lane's byte offset (lk * ld + 2 * lr) * 8, lk <= 3, lr <= 15, in 32 bits: the
+// longest vector stride whose largest offset (3 ld + 30) * 8 still fits
+constexpr int64_t kRotWideMaxLd = ((int64_t)(UINT32_MAX / sizeof(double)) - 2 * 15) / 3;
+static_assert((3 * kRotWideMaxLd + 30) * 8 <= (int64_t)UINT32_MAX && (3 * (kRotWideMaxLd + 1) + 30) * 8 > (int64_t)UINT32_MAX,
+              "kRotWideMaxLd is the last stride without a 32-bit wrap");
+static_assert(kRotWideMaxLd == 178956960, "documented in include/nekkrylov.h and CHANGELOG.md");
 
 template <int MB>
 int launch_rotate_wide(const nkv_layout* L, double* Q, int k, const double* V, int ldv, int n_out, void* stream) {
     constexpr int W = NKV_ROTW_W, U = NKV_ROTW_U;
     auto kern = k_rotate_wide<MB, W, U>;
     const int cp = rotw_cp(MB);
-    const size_t lds = (size_t)rotw_kpad(k) * cp * sizeof(double);
+    const size_t lds = rotw_lds(MB, k);
     static bool attr_set = false;
     if (!attr_set) {
-        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRotLdsMax));
         attr_set = true;
     }
-    const int64_t n_tiles = rows_of(L) / ((int64_t)W * 32);
+    const int64_t n_tiles = rows_of(L) / kRotWideRows;
     if (n_tiles < 1) return NKV_OK;
     // persistent grid: as many workgroups as are resident at once (registers, LDS and waves per CU)
     int per_cu = 0;
@@ -545,17 +573,15 @@ int launch_rotate_wide(const nkv_layout* L, double* Q, int k, const double* V, i
 template <int MB>
 int launch_rotate_chunked(const nkv_layout* L, double* Q, int k, const double* V, int ldv, int n_out,
                                  void* stream) {
-    // past NKV_ROT_CHUNK_W8_MAX 16-column blocks the 4 x MB accumulators need one wave per SIMD
-    // (512 registers)
-    constexpr int W = MB > NKV_ROT_CHUNK_W8_MAX ? 4 : 8;
+    constexpr int W = rot_chunked_waves(MB);
     auto kern = k_rotate_chunked<MB, W>;
     const size_t lds = 2 * (size_t)MB * 16 * 34 * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
-        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        NKV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRotLdsMax));
         attr_set = true;
     }
-    const int64_t n_tiles = rows_of(L) / (W * 16);
+    const int64_t n_tiles = rows_of(L) / rot_chunked_rows(MB);
     if (n_tiles < 1) return NKV_OK;
     int per_cu = (int)((160 * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
@@ -571,8 +597,8 @@ int launch_rotate_few(const nkv_layout* L, double* Q, int k, const double* V, in
     // NO accumulators per row pair: past 8 kept columns fewer row pairs per thread keep the register
     // budget (9-12: 2 pairs x 2 columns in flight, 130 VGPRs at NO = 12; 13-16: 2 x 4) — +32 % at
     // NO = 12 and +10 % at NO = 16 over the MFMA streaming rotation (profiles/r02v_tune_rotf16_E44176.log)
-    constexpr int P = NO <= 8 ? NKV_ROTF_P : 2, U = NO <= 8 ? NKV_ROTF_U : (NO <= 12 ? 2 : 4);
-    const int64_t n_tiles = rows_of(L) / (kThreads * P * 2);
+    constexpr int P = rot_few_pairs(NO), U = NO <= 8 ? NKV_ROTF_U : (NO <= 12 ? 2 : 4);
+    const int64_t n_tiles = rows_of(L) / rot_few_rows(NO);
     if (n_tiles < 1) return NKV_OK;
     // one launch per row band of NKV_ROTF_ROUNDS grid-stride rounds of an NKV_ROTF_G grid, as the DCGS2
     // updates: +17-21 % at N=1e8 over one 1024-workgroup launch (profiles/r02s_tune_rotf*.log)
@@ -591,10 +617,16 @@ int launch_rotate_few(const nkv_layout* L, double* Q, int k, const double* V, in
 
 extern "C" {
 
-int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, int ldv, int n_out, void* stream) {
+// The dispatch of the restart rotation, host only: every argument check, threshold and LDS-fit formula
+// of nkv_rotate_cols lives here; nkv_rotate_cols maps the (path, inst) it gets to a launcher and decides
+// nothing itself.  tests/test_rotate_plan.py restates the rule and walks the whole (k, n_out) table.
+// With the default knobs the table never selects k_rotate_wide<1> or k_rotate_stream<1>: n_out <= 16 is
+// k_rotate_few's.  No test of the default build runs them; the NKV_ROTF_MAX=0 tuning build reaches them, so
+// they stay instantiated.  (A streaming kernel past 8 column blocks is never wanted either: V of 129 or more
+// kept columns, so k >= 129, does not fit LDS whole.)  Every other instantiation is reachable.
+int nkv_rotate_plan(const nkv_layout* L, int k, int ldv, int n_out, int* path, int* inst, int* wg_threads,
+                    int* rows_per_tile) {
     CHECK(check_layout(L));
-    CHECK(check_ptr(Q, "Q"));
-    if (!V_dev) return fail(NKV_EINVAL, "V_dev is NULL");
     // no kernel holds k-sized state (V streams through LDS in k-chunks where it does not fit whole):
     // any k up to NKV_MAX_COLS; every output column lives in registers, so at most NKV_ROT_MAX_OUT
     if (k < 1 || k > NKV_MAX_COLS) return fail(NKV_EINVAL, "rotate: k=%d outside [1, %d]", k, NKV_MAX_COLS);
@@ -602,8 +634,40 @@ int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, 
     if (n_out < 1 || n_out > k) return fail(NKV_EINVAL, "rotate: n_out=%d outside [1, k=%d]", n_out, k);
     if (n_out > NKV_ROT_MAX_OUT)
         return fail(NKV_ESHAPE, "rotate: n_out=%d kept columns > NKV_ROT_MAX_OUT=%d", n_out, NKV_ROT_MAX_OUT);
-    if (n_out <= NKV_ROTF_MAX) {
-        switch (n_out) {
+    if (!path || !inst || !wg_threads || !rows_per_tile) return fail(NKV_EINVAL, "rotate plan: an output is NULL");
+    const int nact = (n_out + 15) / 16;   // 16-column blocks of the MFMA kernels
+    const int64_t rows = rows_of(L);
+    auto plan = [&](int p, int i, int threads, int tile_rows) {
+        *path = p;
+        *inst = i;
+        *wg_threads = threads;
+        *rows_per_tile = tile_rows;
+        return NKV_OK;
+    };
+    // k_rotate_few<n_out>: instantiated for 1..16 kept columns
+    if (n_out <= NKV_ROTF_MAX && n_out <= 16) return plan(NKV_ROT_PATH_FEW, n_out, kThreads, rot_few_rows(n_out));
+    // k_rotate_wide<nact>: instantiated for 1..min(NKV_ROTW_MAX_MB, 8) blocks; V whole in LDS; 32-bit lane offsets
+    if (NKV_ROTW && nact <= NKV_ROTW_MAX_MB && nact <= 8 && rows % kRotWideRows == 0 &&
+        rotw_lds(nact, k) <= kRotLdsMax && L->ld <= kRotWideMaxLd)
+        return plan(NKV_ROT_PATH_WIDE, nact, NKV_ROTW_W * 64, kRotWideRows);
+    // k_rotate_stream<nact>: instantiated for 1..8 blocks; V whole in LDS; 64-bit offsets
+    if (NKV_ROT_STREAM && nact < NKV_ROT_CHUNK_FROM && nact <= 8 &&
+        rows % ((int64_t)NKV_ROT_WAVES * NKV_ROT_NB * 16) == 0 && rot_stream_lds(nact, k) <= kRotLdsMax)
+        return plan(NKV_ROT_PATH_STREAM, nact, rot_stream_waves(nact) * 64, rot_stream_rows(nact));
+    // k_rotate_chunked<2|4|8|12|16>: V through LDS in k-chunks: 17..NKV_ROT_MAX_OUT kept columns where
+    // V[:, 0:n_out] does not fit LDS whole (rows are whole NKV_TILE tiles, so every 16-row slab is full)
+    const int mb = nact <= 2 ? 2 : nact <= 4 ? 4 : nact <= 8 ? 8 : nact <= 12 ? 12 : 16;
+    return plan(NKV_ROT_PATH_CHUNKED, mb, rot_chunked_waves(mb) * 64, rot_chunked_rows(mb));
+}
+
+int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, int ldv, int n_out, void* stream) {
+    CHECK(check_layout(L));
+    CHECK(check_ptr(Q, "Q"));
+    if (!V_dev) return fail(NKV_EINVAL, "V_dev is NULL");
+    int path = 0, inst = 0, wg_threads = 0, rows_per_tile = 0;
+    CHECK(nkv_rotate_plan(L, k, ldv, n_out, &path, &inst, &wg_threads, &rows_per_tile));
+    if (path == NKV_ROT_PATH_FEW) {
+        switch (inst) {
             case 1: return launch_rotate_few<1>(L, Q, k, V_dev, ldv, stream);
             case 2: return launch_rotate_few<2>(L, Q, k, V_dev, ldv, stream);
             case 3: return launch_rotate_few<3>(L, Q, k, V_dev, ldv, stream);
@@ -622,52 +686,44 @@ int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, 
             case 16: return launch_rotate_few<16>(L, Q, k, V_dev, ldv, stream);
             default: break;
         }
-    }
-    if (NKV_ROTW && (n_out + 15) / 16 <= NKV_ROTW_MAX_MB && rows_of(L) % ((int64_t)NKV_ROTW_W * 32) == 0) {
-        const int nact = (n_out + 15) / 16;
-        if ((size_t)rotw_kpad(k) * rotw_cp(nact) * sizeof(double) <= 160 * 1024) {
-            switch (nact) {
-                case 1: return launch_rotate_wide<1>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 2: return launch_rotate_wide<2>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 3: return launch_rotate_wide<3>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 4: return launch_rotate_wide<4>(L, Q, k, V_dev, ldv, n_out, stream);
+    } else if (path == NKV_ROT_PATH_WIDE) {
+        switch (inst) {
+            case 1: return launch_rotate_wide<1>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 2: return launch_rotate_wide<2>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 3: return launch_rotate_wide<3>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 4: return launch_rotate_wide<4>(L, Q, k, V_dev, ldv, n_out, stream);
 #if NKV_ROTW_MAX_MB > 4
-                case 5: return launch_rotate_wide<5>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 6: return launch_rotate_wide<6>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 7: return launch_rotate_wide<7>(L, Q, k, V_dev, ldv, n_out, stream);
-                case 8: return launch_rotate_wide<8>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 5: return launch_rotate_wide<5>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 6: return launch_rotate_wide<6>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 7: return launch_rotate_wide<7>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 8: return launch_rotate_wide<8>(L, Q, k, V_dev, ldv, n_out, stream);
 #endif
-                default: break;
-            }
+            default: break;
+        }
+    } else if (path == NKV_ROT_PATH_STREAM) {
+        switch (inst) {
+            case 1: return launch_rotate_stream<1>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 2: return launch_rotate_stream<2>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 3: return launch_rotate_stream<3>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 4: return launch_rotate_stream<4>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 5: return launch_rotate_stream<5>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 6: return launch_rotate_stream<6>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 7: return launch_rotate_stream<7>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 8: return launch_rotate_stream<8>(L, Q, k, V_dev, ldv, n_out, stream);
+            default: break;
+        }
+    } else if (path == NKV_ROT_PATH_CHUNKED) {
+        switch (inst) {
+            case 2: return launch_rotate_chunked<2>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 4: return launch_rotate_chunked<4>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 8: return launch_rotate_chunked<8>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 12: return launch_rotate_chunked<12>(L, Q, k, V_dev, ldv, n_out, stream);
+            case 16: return launch_rotate_chunked<16>(L, Q, k, V_dev, ldv, n_out, stream);
+            default: break;
         }
     }
-    if (NKV_ROT_STREAM && (n_out + 15) / 16 < NKV_ROT_CHUNK_FROM &&
-        rows_of(L) % ((int64_t)NKV_ROT_WAVES * NKV_ROT_NB * 16) == 0) {
-        const int kp = ((k + 31) & ~31) + 2;
-        const int nact = (n_out + 15) / 16;
-        const size_t lds = (size_t)nact * 16 * kp * sizeof(double);
-        if (lds <= 160 * 1024) {
-            switch (nact) {
-                case 1: return launch_rotate_stream<1>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 2: return launch_rotate_stream<2>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 3: return launch_rotate_stream<3>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 4: return launch_rotate_stream<4>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 5: return launch_rotate_stream<5>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 6: return launch_rotate_stream<6>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 7: return launch_rotate_stream<7>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                case 8: return launch_rotate_stream<8>(L, Q, k, V_dev, ldv, n_out, kp, lds, stream);
-                default: break;
-            }
-        }
-    }
-    // V through LDS in k-chunks: 17..NKV_ROT_MAX_OUT kept columns where V[:, 0:n_out] does not fit
-    // LDS whole (rows are whole NKV_TILE tiles, so every 16-row slab of 8 waves is full)
-    const int nact = (n_out + 15) / 16;
-    if (nact <= 2) return launch_rotate_chunked<2>(L, Q, k, V_dev, ldv, n_out, stream);
-    if (nact <= 4) return launch_rotate_chunked<4>(L, Q, k, V_dev, ldv, n_out, stream);
-    if (nact <= 8) return launch_rotate_chunked<8>(L, Q, k, V_dev, ldv, n_out, stream);
-    if (nact <= 12) return launch_rotate_chunked<12>(L, Q, k, V_dev, ldv, n_out, stream);
-    return launch_rotate_chunked<16>(L, Q, k, V_dev, ldv, n_out, stream);
+    // a missing kernel is an error, never another kernel in its place
+    return fail(NKV_EINVAL, "rotate: no kernel for path %d, instantiation %d", path, inst);
 }
 
 int nkv_rotate(const nkv_layout* L, double* Q, int k, const double* V_dev, int ldv, void* stream) {

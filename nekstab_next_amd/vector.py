@@ -343,8 +343,25 @@ def normalize(q: NekVector) -> float:
     return float(beta.item())
 
 
+ROTATE_PATHS = {_lib.NKV_ROT_PATH_FEW: "few", _lib.NKV_ROT_PATH_WIDE: "wide", _lib.NKV_ROT_PATH_STREAM: "stream",
+                _lib.NKV_ROT_PATH_CHUNKED: "chunked"}
+
+
+def rotate_plan(layout, k: int, n_out: int, ldv: int | None = None) -> tuple[str, int, int, int]:
+    """The kernel ``nkv_rotate_cols`` launches for ``(layout, k, ldv, n_out)``, from the library's own
+    dispatch (``nkv_rotate_plan``, host only: no GPU needed): ``(path, inst, wg_threads, rows_per_tile)``
+    with path one of "few", "wide", "stream", "chunked" and inst that kernel's template parameter.
+    ``layout``: a :class:`NekLayout` or an ``nkv_layout`` struct; ``ldv`` defaults to ``k``."""
+    L = layout.c_struct() if isinstance(layout, NekLayout) else layout
+    out = [ctypes.c_int(0) for _ in range(4)]
+    rc = _lib.load().nkv_rotate_plan(ctypes.byref(L), int(k), int(k if ldv is None else ldv), int(n_out),
+                                     *[ctypes.byref(o) for o in out])
+    _lib.check(rc, "nkv_rotate_plan")
+    return ROTATE_PATHS[out[0].value], out[1].value, out[2].value, out[3].value
+
+
 __all__ = [
     "NekContext", "NekVector", "ComplexNekVector", "Basis", "k_dot", "k_norm", "k_normalize", "k_cmult",
     "k_add2", "k_sub2", "k_sub3", "k_zero", "k_copy", "k_matmul", "combine", "NKV_NORM2",
-    "inner_product", "norm", "normalize",
+    "inner_product", "norm", "normalize", "rotate_plan", "ROTATE_PATHS",
 ]

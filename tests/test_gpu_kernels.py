@@ -17,7 +17,7 @@ from nekstab_next_amd._lib import NKV_NORM2, NKV_TIME, NkvError, NkvNaNError
 from nekstab_next_amd.arnoldi import HessenbergDev, arnoldi_factorization
 from nekstab_next_amd.layout import NekLayout
 from nekstab_next_amd.operators import DiagOperator, Rot2Operator
-from nekstab_next_amd.vector import NekContext, k_matmul, k_normalize
+from nekstab_next_amd.vector import NekContext, k_matmul, k_normalize, rotate_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -207,10 +207,27 @@ def test_rotate_vs_oracle(gpu, k):
     np.testing.assert_array_equal(syn.to_reference_order(lay, got[k]), Qref[k])  # column k untouched
 
 
+# The kernel and instantiation each (k, n_out) below runs on LAYOUTS["2d"], asserted through nkv_rotate_plan
+# before the call.  k_rotate_wide<1> and k_rotate_stream<1> are unreachable in the default build (n_out <= 16
+# is k_rotate_few's); k_rotate_stream<2..4> and k_rotate_chunked<2> run in tests/test_gpu_rotate_paths.py.
+ROTATE_KERNEL = {
+    (7, 3): ("few", 3), (100, 1): ("few", 1), (128, 6): ("few", 6), (128, 8): ("few", 8), (9, 9): ("few", 9),
+    (4, 4): ("few", 4), (131, 5): ("few", 5), (576, 7): ("few", 7), (128, 12): ("few", 12), (130, 13): ("few", 13),
+    (64, 16): ("few", 16), (1000, 11): ("few", 11), (900, 6): ("few", 6),
+    (128, 20): ("wide", 2), (129, 17): ("wide", 2), (128, 25): ("wide", 2), (100, 17): ("wide", 2),
+    (17, 17): ("wide", 2), (18, 18): ("wide", 2), (130, 48): ("wide", 3), (129, 33): ("wide", 3),
+    (37, 33): ("wide", 3), (200, 40): ("wide", 3), (64, 64): ("wide", 4), (250, 64): ("wide", 4),
+    (83, 70): ("stream", 5), (128, 65): ("stream", 5), (96, 96): ("stream", 6), (150, 100): ("stream", 7),
+    (128, 128): ("stream", 8),
+    (576, 33): ("chunked", 4), (256, 100): ("chunked", 8), (200, 128): ("chunked", 8), (300, 150): ("chunked", 12),
+    (256, 255): ("chunked", 16), (576, 256): ("chunked", 16),
+}
+
+
 @pytest.mark.parametrize("k,n_out", [(7, 3), (100, 1), (128, 6), (128, 8), (9, 9), (4, 4), (131, 5), (576, 7),
                                      (128, 12), (130, 13), (64, 16), (1000, 11), (128, 20), (129, 17), (256, 255),
                                      (300, 150), (576, 33), (900, 6), (256, 100), (200, 128), (576, 256),
-                                     # k_rotate_wide (17-64 kept, V in LDS): every column-block count, whole
+                                     # k_rotate_wide (17-64 kept, V in LDS): 2, 3 and 4 column blocks, whole
                                      # and partial last batches (k % 16), one-batch k, k = n_out
                                      (128, 25), (100, 17), (130, 48), (64, 64), (129, 33), (37, 33), (17, 17),
                                      (200, 40), (18, 18), (250, 64),
@@ -220,6 +237,7 @@ def test_rotate_vs_oracle(gpu, k):
 def test_rotate_cols_vs_oracle(gpu, k, n_out):
     """Partial restart rotation: Q[:, :n_out] = Q[:, :k] V[:, :n_out]; columns n_out..k untouched."""
     lay = LAYOUTS["2d"]
+    assert rotate_plan(lay, k, n_out)[:2] == ROTATE_KERNEL[k, n_out]
     ctx, _ = make_ctx(lay)
     L = olayout(lay)
     Q = ctx.basis(k + 1)
@@ -248,12 +266,13 @@ def test_rotate_cols_vs_oracle(gpu, k, n_out):
 def test_rotate_cols_row_bands(gpu, n_out):
     """The few-column rotation issues one dispatch per row band (NKV_ROTF_ROUNDS): at N=2.26e6
     (E=1000, 3-D) a call spans several bands; every band's rows equal Q V to 1e-12 and the
-    columns past n_out are untouched (n_out=17 runs the MFMA streaming kernel beside it)."""
+    columns past n_out are untouched (n_out=17 runs the wide-load MFMA kernel k_rotate_wide<2> beside it)."""
     from nekstab_next_amd.layout import box3d_layout
 
     lay = box3d_layout(1000)
-    ctx, _ = make_ctx(lay)
     k = 20
+    assert rotate_plan(lay, k, n_out)[:2] == {6: ("few", 6), 12: ("few", 12), 16: ("few", 16), 17: ("wide", 2)}[n_out]
+    ctx, _ = make_ctx(lay)
     Q = ctx.basis(k + 1)
     for i in range(k + 1):
         Q[i].fill_hash(300 + i)
