@@ -819,6 +819,44 @@ int nkv_rk4_stage(const nkv_layout* L, const double* v, int64_t v_stride, const 
                   const double* acc, int64_t acc_stride, double* w, int64_t w_stride, double* acc_out,
                   int64_t ao_stride, int nfld, int zero_rest, void* stream);
 
+/* ---- time-periodic base flow of the Burgers flow: the orbit, its tangent and the harmonic forcing -----
+ * What nekStab's periodic half needs on one mesh: the forced UPO Newton (uparam(1) = 2.2,
+ * newton_krylov.f90:77-91,128-131), Floquet direct / adjoint / intracycle growth (3.11 / 3.21 / 3.31,
+ * matvec.f90:176-235,414-468) about the stored orbit uor/vor/wor/tor (ifstorebase) or with the nonlinear flow
+ * and the perturbation advanced side by side (ifbase = .true.).  Conventions, arithmetic and the treatment of
+ * bad arguments and empty shards: as for the advection-diffusion entries above.
+ *
+ * nkv_burgers_tangent_rhs: replaces the two solver calls of an ifbase = .true. step (the nonlinear and the
+ *   linearised convection of one stage).  For a base state B and a perturbation u of nfld fields each, one
+ *   tiled pass writes both LOCAL right-hand sides
+ *     r_B,f = r_advdiff,f(B; U = B_vel)               the bits of forward nkv_advdiff_rhs with u = U = B
+ *     r_u,f = forward nkv_linconv_rhs(u; B)_f         the same bits
+ *   Coordinates and geometric factors once per element group; B_f staged once, its derivatives feeding the
+ *   self-advection, the diffusion flux of B and the production term.  19 doubles per point move at ldim = 3,
+ *   nfld = 4 where the two launches move 29.  LDS as nkv_linconv_rhs (the flux tiles serve B, then u).
+ *   nfld >= ldim; the spans of r_B and r_u must not meet each other, u or B.
+ * nkv_orbit_stage: one RK4 stage of the base flow under the harmonic forcing g(t) = g0 + cos(wt) gc +
+ *   sin(wt) gs (nekStab forces through userf; here the three parts are fields and c, s the cos and sin of the
+ *   stage's phase, formed by the host) and, when tr is not NULL, of the tangent in the same launch.  Base half,
+ *   per point, in this order:
+ *     k = minv r [+ g0] [+ c gc] [+ s gs]      w = v + a k      acc' = (first ? v : acc) + b k
+ *   each of g0, gc, gs may be NULL (one g_stride).  Tangent half (tv, tr, tacc, tw, tacc_out): nkv_rk4_stage
+ *   without g, with the same a, b, first.  NULL conventions and aliasing per half as nkv_rk4_stage: acc_out may
+ *   be the acc or the v of its own half, nothing else may meet an output, of either half.  w is the next
+ *   stage's state: pointed into an orbit buffer it stores the orbit with no pass of its own.  zero_rest: bit 0
+ *   zeroes pressure and time behind acc_out, bit 1 behind tacc_out (each then a whole state vector).  With
+ *   gc = gs = NULL and no tangent half: the bits of nkv_rk4_stage. */
+int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                            const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                            const double* u, int nfld, int64_t u_stride, double* r_B, int64_t rB_stride, double* r_u,
+                            int64_t ru_stride, void* stream);
+int nkv_orbit_stage(const nkv_layout* L, const double* minv, const double* v, int64_t v_stride, const double* r,
+                    int64_t r_stride, const double* g0, const double* gc, const double* gs, int64_t g_stride, double c,
+                    double s, double a, double b, int first, const double* acc, int64_t acc_stride, double* w,
+                    int64_t w_stride, double* acc_out, int64_t ao_stride, const double* tv, int64_t tv_stride,
+                    const double* tr, int64_t tr_stride, const double* tacc, int64_t tacc_stride, double* tw,
+                    int64_t tw_stride, double* tacc_out, int64_t tao_stride, int nfld, int zero_rest, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

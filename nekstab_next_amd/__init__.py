@@ -16,7 +16,7 @@ def __getattr__(name):
 
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
                 "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
-                "postproc", "vortex", "forcing", "monitors", "gs", "advdiff", "resolvent", "burgers",
+                "postproc", "vortex", "forcing", "monitors", "gs", "advdiff", "resolvent", "burgers", "orbit",
                 "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
@@ -32,4 +32,6 @@ def __getattr__(name):
         return getattr(importlib.import_module(".resolvent", __name__), name)
     if name in ("LinearisedConvection", "ViscousBurgers"):   # the nonlinear flow and its linearisation (burgers.py)
         return getattr(importlib.import_module(".burgers", __name__), name)
+    if name in ("OrbitFlow", "OrbitPropagator"):   # the time-periodic base flow and its tangent (orbit.py)
+        return getattr(importlib.import_module(".orbit", __name__), name)
     raise AttributeError(name)

@@ -159,6 +159,11 @@ _SIGNATURES = {
                                 c_int, _P]),
     "nkv_rk4_stage": (c_int, [_L, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_int, _P, c_int64,
                               _P, c_int64, _P, c_int64, c_int, c_int, _P]),
+    "nkv_burgers_tangent_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int64, _P,
+                                        c_int64, _P, c_int64, _P]),
+    "nkv_orbit_stage": (c_int, [_L, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_double, c_double, c_double,
+                                c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

@@ -12,6 +12,9 @@
 // Further down: the same right-hand side with the production term of a base state B of all fields
 // (k_linconv_rhs: the linearisation of the viscous Burgers flow of burgers.py and its adjoint) and the
 // classical RK4 stage of that flow (k_rk4_stage); its nonlinear right-hand side is k_advdiff_rhs with U = u.
+// Last: the periodic orbits of that flow (orbit.py) — the nonlinear and the linearised right-hand side of a
+// base state and a perturbation advanced side by side in one pass (k_burgers_tangent_rhs) and the RK4 stage
+// under a harmonic forcing that writes the orbit, with the tangent's stage in the same launch (k_orbit_stage).
 #include "nkv_internal.h"
 
 namespace {
@@ -504,6 +507,222 @@ __global__ __launch_bounds__(kThreads) void k_rk4_stage(int64_t n, const double*
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The base flow and its tangent side by side (nekStab's ifbase = .true.: the nonlinear flow and the
+// perturbation advance together): for a base state B and a perturbation u of nfld fields each, one tiled pass
+// writes both local right-hand sides
+//   rB_f = r_advdiff,f(B; U = B_vel)                                   (the bits of k_advdiff_rhs<.., false>)
+//   ru_f = r_advdiff,f(u; U = B_vel) - bm1 sum_{d<LDIM} u_d d_d B_f    (the bits of k_linconv_rhs<.., false>)
+// The coordinates are staged and the factors formed once per group; B_f is staged once and its line sums
+// feed the self-advection sum_d B_d d_d B_f, the diffusion flux of B and the production term.  The three flux
+// tiles serve B and then u, so the footprint stays k_linconv_rhs's: lx1^2 + (LDIM + 2) nt doubles.  Only
+// the production term waits in a register between the two halves of a field.  Every read of the field tiles
+// lies before the field's last barrier, so the next field is staged without one of its own: four barriers
+// per field, where the two kernels take three each.  Each output keeps the operand order of the kernel it
+// restates.  The launch bounds ask for 4 waves per SIMD (128 VGPRs, as k_linconv_rhs reaches unasked): two
+// 512-thread workgroups per CU at lx1 = 8 in 3-D, for about ten spilled registers.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>()), 4) void k_burgers_tangent_rhs(
+    int64_t nel, int epb, int nfld, const double* __restrict__ Dg, const double* __restrict__ wg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ B, int64_t b_stride, const double* __restrict__ kappa, const double* __restrict__ u,
+    int64_t u_stride, double* __restrict__ rB, int64_t rb_stride, double* __restrict__ ru, int64_t ru_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    const int nt = epb * pts;
+    double* D = lds;                         // D(i, m) at D[i*NX + m]
+    double* X = D + NX * NX;                 // coordinates, then the flux along r (of B, then of u)
+    double* Y = X + nt;                      // ... along s
+    double* Z = Y + nt;                      // ... along t (3-D only)
+    double* U = LDIM == 3 ? Z + nt : Z;      // the perturbation field being differentiated
+    double* Bt = U + nt;                     // the base field being differentiated
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const PointIndex<LDIM, NX> ix(tid);
+    const double wt = ix.weight(wg);
+    const int le = tid / pts;
+    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = D + ix.j;
+    const double* Dck = D + ix.k;
+    // sum_a D_a^T of the fluxes in the three tiles
+    auto transposed_sums = [&]() {
+        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) {
+            tr = tr + Dci[m * NX] * X[q.ri + m];
+            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+        }
+        double acc = tr + ts;
+        if constexpr (LDIM == 3) {
+            double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+            acc = acc + tt;
+        }
+        return acc;
+    };
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double jacmi = 1.0 / jac;
+        const double bm = jac * wt;
+        double Ub[LDIM];       // the advecting velocity B_d
+        double P[LDIM];        // the velocity perturbation u_d
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) {
+            Ub[d] = live ? B[d * b_stride + p] : 0.0;
+            P[d] = live ? u[d * u_stride + p] : 0.0;
+        }
+        double* tiles[3] = {X, Y, Z};
+        for (int f = 0; f < nfld; ++f) {
+            // (every lane differentiated the previous field before that field's last barrier)
+            if (live) {
+                U[tid] = u[f * u_stride + p];
+                Bt[tid] = B[f * b_stride + p];
+            }
+            __syncthreads();   // (and every lane has formed its factors / read the previous fluxes of u)
+            double advB = 0.0, advu = 0.0, prod = 0.0;
+            const double kb = live ? -kappa[f] * bm : 0.0;
+            // the fluxes F_a of one staged field into the three tiles; its advection by B_vel is returned
+            auto fluxes = [&](const double* T, double& adv, bool production) {
+                double tr, ts, tt;
+                line_sums<LDIM, NX>(q, T, tr, ts, tt);
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double dd = physical_derivative<LDIM>(g, jacmi, d, tr, ts, tt);
+                    G[d] = kb * dd;
+                    adv = adv + Ub[d] * dd;
+                    if (production) prod = d == 0 ? P[0] * dd : prod + P[d] * dd;
+                }
+#pragma unroll
+                for (int a = 0; a < LDIM; ++a) {
+                    double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+                    tiles[a][tid] = F;
+                }
+            };
+            if (live) fluxes(Bt, advB, true);
+            __syncthreads();
+            if (live) rB[f * rb_stride + p] = transposed_sums() - bm * advB;
+            __syncthreads();   // the fluxes of B are read
+            if (live) fluxes(U, advu, false);
+            __syncthreads();
+            if (live) ru[f * ru_stride + p] = (transposed_sums() - bm * advu) - bm * prod;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// One RK4 stage of the base flow under a harmonic forcing and, optionally, of its tangent in the same launch
+// (grid.y = field).  Base half, per point, in this order, no contraction:
+//   k = m r [+ g0] [+ c gc] [+ s gs]      w = v + a k      acc' = (first ? v : acc) + b k
+// c, s: the cos and sin of the stage's phase, formed by the host.  Tangent half: k_rk4_stage without g, on
+// its own v, r, acc, w and acc'; a NULL r skips it.  A block runs the base half of its points, then the
+// tangent half (m comes from the cache the second time).  The NULL conventions, the zeroing and VEC as in
+// k_rk4_stage.
+// ------------------------------------------------------------------------------------------
+struct StageHalf {
+    const double *v, *r, *acc;
+    double *w, *ao;
+    int64_t v_stride, r_stride, acc_stride, w_stride, ao_stride;
+    double *zero_p, *zero_t;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_orbit_stage(int64_t n, const double* __restrict__ m, StageHalf hb,
+                                                          const double* __restrict__ g0, const double* __restrict__ gc,
+                                                          const double* __restrict__ gs, int64_t g_stride, double c,
+                                                          double s, StageHalf ht, double a, double b, int first,
+                                                          int64_t n_p) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.y;
+    const double* g0f = g0 ? g0 + f * g_stride : nullptr;
+    const double* gcf = gc ? gc + f * g_stride : nullptr;
+    const double* gsf = gs ? gs + f * g_stride : nullptr;
+    const int64_t t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x, step = (int64_t)gridDim.x * kThreads;
+    for (int half = 0; half < 2; ++half) {
+        const StageHalf& h = half ? ht : hb;
+        if (!h.r) continue;   // no tangent half
+        const bool forced = half == 0;
+        const double* vf = h.v ? h.v + f * h.v_stride : nullptr;
+        const double* rf = h.r + f * h.r_stride;
+        const double* af = first ? vf : h.acc + f * h.acc_stride;
+        double* wf = h.w ? h.w + f * h.w_stride : nullptr;
+        double* of = h.ao + f * h.ao_stride;
+        auto point = [&](int64_t p) {
+            double k = m[p] * rf[p];
+            if (forced) {
+                if (g0f) k = k + g0f[p];
+                if (gcf) k = k + c * gcf[p];
+                if (gsf) k = k + s * gsf[p];
+            }
+            const double sa = a * k, t = b * k;
+            const double base = af ? af[p] : 0.0;
+            if (wf) wf[p] = vf ? vf[p] + sa : sa;
+            of[p] = af ? base + t : t;
+        };
+        if constexpr (VEC) {
+            const int64_t pairs = n / 2;
+            for (int64_t i = t0; i < pairs; i += step) {
+                const int64_t p = 2 * i;
+                const double2 mm = ld2(m + p), rr = ld2(rf + p);
+                double2 k = make_double2(mm.x * rr.x, mm.y * rr.y);
+                if (forced) {
+                    if (g0f) {
+                        const double2 gg = ld2(g0f + p);
+                        k = make_double2(k.x + gg.x, k.y + gg.y);
+                    }
+                    if (gcf) {
+                        const double2 gg = ld2(gcf + p);
+                        k = make_double2(k.x + c * gg.x, k.y + c * gg.y);
+                    }
+                    if (gsf) {
+                        const double2 gg = ld2(gsf + p);
+                        k = make_double2(k.x + s * gg.x, k.y + s * gg.y);
+                    }
+                }
+                const double2 t = make_double2(b * k.x, b * k.y);
+                double2 o = t;
+                if (af) {   // (read before w is written: acc_out may be v)
+                    const double2 base = ld2(af + p);
+                    o = make_double2(base.x + t.x, base.y + t.y);
+                }
+                if (wf) {
+                    double2 sa = make_double2(a * k.x, a * k.y);
+                    if (vf) {
+                        const double2 vv = ld2(vf + p);
+                        sa = make_double2(vv.x + sa.x, vv.y + sa.y);
+                    }
+                    st2(wf + p, sa);
+                }
+                st2(of + p, o);
+            }
+            if ((n & 1) && t0 == 0) point(n - 1);
+        } else {
+            for (int64_t p = t0; p < n; p += step) point(p);
+        }
+        if (f == 0 && h.zero_p) {
+            for (int64_t p = t0; p < n_p; p += step) h.zero_p[p] = 0.0;
+            if (t0 == 0) *h.zero_t = 0.0;
+        }
+    }
+}
+
 template <int LDIM, int NX>
 void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
                 const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
@@ -550,6 +769,19 @@ void launch_linconv(int64_t nel, int nfld, const double* D, const double* w, con
     else
         hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
                            epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
+}
+
+template <int LDIM, int NX>
+void launch_tangent(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
+                    const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u,
+                    int64_t u_stride, double* rB, int64_t rb_stride, double* ru, int64_t ru_stride, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    hipLaunchKernelGGL((k_burgers_tangent_rhs<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
+                       nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, rB, rb_stride, ru, ru_stride);
 }
 
 }  // namespace
@@ -818,6 +1050,160 @@ int nkv_rk4_stage(const nkv_layout* L, const double* v, int64_t v_stride, const 
     else
         hipLaunchKernelGGL(k_rk4_stage<false>, grid, dim3(kThreads), 0, S(stream), n, vv, v_stride, minv, r, r_stride, g,
                            g_stride, a, b, first ? 1 : 0, aa, acc_stride, w, w_stride, acc_out, ao_stride, zp, L->n_p, zt);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                            const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                            const double* u, int nfld, int64_t u_stride, double* r_B, int64_t rB_stride, double* r_u,
+                            int64_t ru_stride, void* stream) {
+    static const char who[] = "burgers_tangent_rhs";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
+                                 nfld, ldim);
+    if (B_stride < L->n_v || u_stride < L->n_v || rB_stride < L->n_v || ru_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: strides B_stride=%lld u_stride=%lld rB_stride=%lld ru_stride=%lld below n_v=%lld",
+                    who, (long long)B_stride, (long long)u_stride, (long long)rB_stride, (long long)ru_stride,
+                    (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(B, who, "B"));
+    CHECK(need(kappa, who, "kappa"));
+    CHECK(need(u, who, "u"));
+    CHECK(need(r_B, who, "r_B"));
+    CHECK(need(r_u, who, "r_u"));
+    // both results are written field by field while later fields of u and B are still to be read
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        const double* pe = p + (int64_t)(nfld - 1) * ps + L->n_v;
+        const double* oe = o + (int64_t)(nfld - 1) * os + L->n_v;
+        return p < oe && o < pe;
+    };
+    if (meets(r_B, rB_stride, r_u, ru_stride)) return fail(NKV_EINVAL, "%s: r_B overlaps r_u", who);
+    if (meets(u, u_stride, r_B, rB_stride) || meets(B, B_stride, r_B, rB_stride))
+        return fail(NKV_EINVAL, "%s: r_B overlaps u or B", who);
+    if (meets(u, u_stride, r_u, ru_stride) || meets(B, B_stride, r_u, ru_stride))
+        return fail(NKV_EINVAL, "%s: r_u overlaps u or B", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_BT_RHS(NX)                                                                                              \
+    case NX:                                                                                                        \
+        if (ldim == 3)                                                                                              \
+            launch_tangent<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r_B, rB_stride, r_u, \
+                                  ru_stride, st);                                                                   \
+        else                                                                                                        \
+            launch_tangent<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r_B, rB_stride, r_u, \
+                                  ru_stride, st);                                                                   \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_BT_RHS) }
+#undef NKV_BT_RHS
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_orbit_stage(const nkv_layout* L, const double* minv, const double* v, int64_t v_stride, const double* r,
+                    int64_t r_stride, const double* g0, const double* gc, const double* gs, int64_t g_stride, double c,
+                    double s, double a, double b, int first, const double* acc, int64_t acc_stride, double* w,
+                    int64_t w_stride, double* acc_out, int64_t ao_stride, const double* tv, int64_t tv_stride,
+                    const double* tr, int64_t tr_stride, const double* tacc, int64_t tacc_stride, double* tw,
+                    int64_t tw_stride, double* tacc_out, int64_t tao_stride, int nfld, int zero_rest, void* stream) {
+    static const char who[] = "orbit_stage";
+    CHECK(check_layout(L));
+    const int64_t n = L->n_v;
+    if (n == 0) return NKV_OK;   // an empty shard: nothing to touch
+    if (nfld < 1 || nfld > 65535) return fail(NKV_EINVAL, "%s: nfld=%d outside 1..65535", who, nfld);
+    const bool tan = tr != nullptr;
+    if (!tan && (tv || tacc || tw || tacc_out))
+        return fail(NKV_EINVAL, "%s: tr is NULL (no tangent half) but another tangent pointer is not", who);
+    if (zero_rest < 0 || zero_rest > 3 || ((zero_rest & 2) && !tan))
+        return fail(NKV_EINVAL, "%s: zero_rest=%d (bit 0: acc_out, bit 1: tacc_out of a tangent half)", who, zero_rest);
+    const bool forced = g0 || gc || gs;
+    if (forced && g_stride < n) return fail(NKV_EINVAL, "%s: g_stride=%lld below n_v=%lld", who, (long long)g_stride,
+                                            (long long)n);
+    CHECK(need(minv, who, "minv"));
+    CHECK(need(r, who, "r"));
+    CHECK(need(acc_out, who, "acc_out"));
+    if (tan) CHECK(need(tacc_out, who, "tacc_out"));
+    if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c) || !std::isfinite(s))
+        return fail(NKV_EINVAL, "%s: a=%g b=%g c=%g s=%g", who, a, b, c, s);
+    const bool need_acc = !first;
+    // one half as k_rk4_stage takes it: v = NULL stands for zero; v is read when first or w is given
+    struct Half {
+        const double *v, *r, *acc;
+        double *w, *ao;
+        int64_t vs, rs, as, ws, os;
+    };
+    Half H[2] = {{(first || w) ? v : nullptr, r, need_acc ? acc : nullptr, w, acc_out, v_stride, r_stride, acc_stride,
+                  w_stride, ao_stride},
+                 {(first || tw) ? tv : nullptr, tr, need_acc ? tacc : nullptr, tw, tacc_out, tv_stride, tr_stride,
+                  tacc_stride, tw_stride, tao_stride}};
+    const int nh = tan ? 2 : 1;
+    for (int h = 0; h < nh; ++h) {
+        const Half& x = H[h];
+        if (need_acc) CHECK(need(x.acc, who, h ? "tacc" : "acc"));
+        if ((x.v && x.vs < n) || x.rs < n || (x.acc && x.as < n) || (x.w && x.ws < n) || x.os < n)
+            return fail(NKV_EINVAL,
+                        "%s: %s half: strides v=%lld r=%lld acc=%lld w=%lld acc_out=%lld below n_v=%lld", who,
+                        h ? "tangent" : "base", (long long)x.vs, (long long)x.rs, (long long)x.as, (long long)x.ws,
+                        (long long)x.os, (long long)n);
+    }
+    // acc_out may be the acc or the v of its own half exactly (pointwise); otherwise no output span meets
+    // another operand's, of either half
+    auto end = [&](const double* p, int64_t stride) { return p + (int64_t)(nfld - 1) * stride + n; };
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        return p && o && p < end(o, os) && o < end(p, ps);
+    };
+    auto out_bad = [&](int h, const double* o, int64_t os, bool may_alias) {
+        if (meets(minv, 0, o, os) || meets(g0, g_stride, o, os) || meets(gc, g_stride, o, os) ||
+            meets(gs, g_stride, o, os))
+            return true;
+        for (int k = 0; k < nh; ++k) {
+            const Half& x = H[k];
+            const bool own = may_alias && k == h;
+            if (meets(x.r, x.rs, o, os)) return true;
+            if (meets(x.v, x.vs, o, os) && !(own && x.v == o && x.vs == os)) return true;
+            if (meets(x.acc, x.as, o, os) && !(own && x.acc == o && x.as == os)) return true;
+        }
+        return false;
+    };
+    bool bad = false;
+    for (int h = 0; h < nh; ++h) {
+        const Half& x = H[h];
+        bad = bad || out_bad(h, x.ao, x.os, true) || (x.w && (out_bad(h, x.w, x.ws, false) || meets(x.w, x.ws, x.ao, x.os)));
+    }
+    if (tan)
+        bad = bad || meets(H[0].ao, H[0].os, H[1].ao, H[1].os) || meets(H[0].ao, H[0].os, H[1].w, H[1].ws) ||
+              meets(H[0].w, H[0].ws, H[1].ao, H[1].os) || meets(H[0].w, H[0].ws, H[1].w, H[1].ws);
+    if (bad)
+        return fail(NKV_EINVAL, "%s: w or acc_out overlaps an operand (only acc_out may be the acc or v of its half)", who);
+    for (int h = 0; h < nh; ++h)
+        if ((zero_rest & (1 << h)) && (nfld != L->n_wf || H[h].os != L->sv))
+            return fail(NKV_EINVAL,
+                        "%s: zero_rest needs %s to be a state vector (nfld=%d, n_wf=%d, ao_stride=%lld, sv=%lld)", who,
+                        h ? "tacc_out" : "acc_out", nfld, L->n_wf, (long long)H[h].os, (long long)L->sv);
+    auto a16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    auto ok = [&](const void* p, int64_t stride) { return !p || (a16(p) && stride % 2 == 0); };
+    bool vec = n >= 2 && a16(minv) && ok(g0, g_stride) && ok(gc, g_stride) && ok(gs, g_stride);
+    StageHalf K[2] = {};
+    for (int h = 0; h < nh; ++h) {
+        const Half& x = H[h];
+        vec = vec && ok(x.v, x.vs) && ok(x.r, x.rs) && ok(x.acc, x.as) && ok(x.w, x.ws) && ok(x.ao, x.os);
+        const bool z = zero_rest & (1 << h);
+        K[h] = StageHalf{x.v, x.r, x.acc, x.w, x.ao, x.vs, x.rs, x.as, x.ws, x.os,
+                         z ? x.ao + (int64_t)L->n_wf * L->sv : nullptr, z ? x.ao + rows_of(L) : nullptr};
+    }
+    const dim3 grid(grid_for(vec ? n / 2 : n, 1024), nfld);
+    if (vec)
+        hipLaunchKernelGGL(k_orbit_stage<true>, grid, dim3(kThreads), 0, S(stream), n, minv, K[0], g0, gc, gs, g_stride, c,
+                           s, K[1], a, b, first ? 1 : 0, L->n_p);
+    else
+        hipLaunchKernelGGL(k_orbit_stage<false>, grid, dim3(kThreads), 0, S(stream), n, minv, K[0], g0, gc, gs, g_stride,
+                           c, s, K[1], a, b, first ? 1 : 0, L->n_p);
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -13,9 +13,13 @@ Reference: ``core/newton_krylov.f90:1-166``.  Per Newton iteration i (at most 10
 and on convergence q is written as the base flow ``BF_<session>0.f00001`` (:155-164).  The
 caller supplies ``nonlinear(q, f)`` (f <- F(q)) and ``linearized(q)`` (a LinearOperator: the
 forward map of the linearisation about q; for uparam(1) = 2.1 wrap the period row with
-:class:`~.operators.LegacyMatvec` yourself and pass ``mode=2.1``).  Out of scope, as in SURVEY §2:
-the dynamic tolerance schedule (``ifdyntol``, ``spec_tole``, :93, :114-117, :383-435), the orbit
-storage for UPOs (:82-91) and the Nek5000 output of intermediate iterates (``nwt``, ``ic_``)."""
+:class:`~.operators.LegacyMatvec` yourself and pass ``mode=2.1``).  For a forced periodic orbit
+(uparam(1) = 2.2) the orbit storage of :82-91 is :class:`~.orbit.OrbitFlow`'s: pass its ``residual``
+and ``linearized`` with ``mode=2.2`` — the linearised map is then the tangent about the stored orbit
+(orbit.OrbitFlow keeps the stage states, as ``ifstorebase`` keeps uor/vor/wor/tor).  Out of scope, as
+in SURVEY §2: the dynamic tolerance schedule (``ifdyntol``, ``spec_tole``, :93, :114-117, :383-435),
+the natural UPO loop of 2.1 whose period changes per iterate, and the Nek5000 output of
+intermediate iterates (``nwt``, ``ic_``)."""
 from __future__ import annotations
 
 import os
