@@ -385,6 +385,64 @@ int nkv_rotate_cols(const nkv_layout* L, double* Q, int k, const double* V_dev, 
 int nkv_rotate_plan(const nkv_layout* L, int k, int ldv, int n_out, int* path, int* inst, int* wg_threads,
                     int* rows_per_tile);
 
+/* The launch shape of a streaming entry point (the Gram–Schmidt family, BLAS-1, nkv_op_diag) for
+ * (L, op, j, flags).  Host only: no device work, callable without a GPU.  Every launcher decides through
+ * this function and only maps the plan to its launches, so the two never disagree; every size threshold
+ * and band formula of the family lives in it (csrc/core.hip).
+ *   op    : NKV_STREAM_BLOCK_DOT   nkv_block_dot (nkv_dot is j = 1)             j = columns, 1..NKV_MAX_COLS
+ *           NKV_STREAM_BLOCK_UPDATE nkv_block_update, nkv_combine                j = columns, >= 0
+ *           NKV_STREAM_UPDATE_DOT  nkv_block_update_dot                          j = columns, 1..NKV_MAX_COLS
+ *           NKV_STREAM_BLOCK_DOT2  nkv_block_dot2                                j = columns, 1..NKV_MAX_COLS
+ *           NKV_STREAM_DCGS2_UPDATE nkv_dcgs2_update                             j = m, >= 0
+ *           NKV_STREAM_AXPY_DOT    nkv_axpy_dot                                  j ignored
+ *           NKV_STREAM_BLAS1       nkv_zero/copy/scal/axpby/sub3/axpy_dev        j ignored
+ *           NKV_STREAM_OP_DIAG     nkv_op_diag                                   j ignored
+ *           NKV_STREAM_FINISH      nkv_normalize_dev/normalize_store/arnoldi_finish (and the closing
+ *                                  normalisation of nkv_mgs2_step)               j ignored
+ *   flags : only what changes the shape is read: NKV_NORM2 (block update: the fused norm; DCGS2 update:
+ *           "nrm2_dev given"), NKV_OVERWRITE (block update), NKV_X_IS_LAST (two-vector dot).
+ * The plan:
+ *   kernel        : op, or NKV_STREAM_SPLIT for nkv_block_update_dot past 256 columns or 2^29 rows: that call
+ *                   runs the plans of NKV_STREAM_BLOCK_UPDATE then NKV_STREAM_BLOCK_DOT (every other field 0)
+ *   pairs         : double2 per thread per tile, the kernel's template parameter (fused pass: 1)
+ *   nw, cpw       : fused pass k_update_dot<nw, cpw>: waves per workgroup, columns per wave (else 0)
+ *   wg_threads, rows_per_tile : threads per workgroup; rows one workgroup handles per trip of its loop
+ *   tiles         : the items the grid's loop walks: row tiles of the whole vector (updates, nkv_axpy_dot), row
+ *                   tiles of ONE weighted field (the two dots: grid.y or the block's field loop covers the fields),
+ *                   chunks of rows_per_tile rows (BLAS-1, finish, op_diag)
+ *   grid_x, grid_y: the first launch's grid
+ *   launches      : kernel launches ("row bands"; 0: an empty shard's dot launches only its second stage)
+ *   band_tiles    : items per launch (launch i walks [i band_tiles, min((i+1) band_tiles, tiles)))
+ *   last_grid_x   : grid.x of the last launch (launches between the first and the last use grid_x)
+ *   work_loop     : NKV_STREAM_LOOP_TILES: one item per trip.  NKV_STREAM_LOOP_UNITS (DCGS2 update with norm
+ *                   only): one row tile of EVERY weighted field per trip, then the pressure tiles one by one
+ *   units         : trips of that loop summed over the grid (a workgroup takes a second trip iff units > grid)
+ *   fields_per_block : weighted fields one block walks per row tile (two-vector dot; else 1)
+ *   partial_slots, partial_cols : reduction partials per column, and columns, that the second stage sums
+ *                   (0: no reduction); grid_x * grid_y * partial_cols slots are written at the most and
+ *                   must fit nkv_workspace_bytes(L, max_cols) — max_cols >= the columns of the call
+ * NKV_FUSE_ROUNDS and NKV_AXD_ROUNDS are 0 in the product build, so NKV_STREAM_UPDATE_DOT and
+ * NKV_STREAM_AXPY_DOT always report one launch; the block update, the DCGS2 update without norm and op_diag
+ * launch bands once the vector holds two bands of NKV_*_ROUNDS grid-stride rounds.
+ * The status of a bad layout or j is the launcher's own; a NULL plan or an unknown op is NKV_EINVAL. */
+#define NKV_STREAM_BLOCK_DOT 1
+#define NKV_STREAM_BLOCK_UPDATE 2
+#define NKV_STREAM_UPDATE_DOT 3
+#define NKV_STREAM_BLOCK_DOT2 4
+#define NKV_STREAM_DCGS2_UPDATE 5
+#define NKV_STREAM_AXPY_DOT 6
+#define NKV_STREAM_BLAS1 7
+#define NKV_STREAM_OP_DIAG 8
+#define NKV_STREAM_FINISH 9
+#define NKV_STREAM_SPLIT 10
+#define NKV_STREAM_LOOP_TILES 1
+#define NKV_STREAM_LOOP_UNITS 2
+typedef struct nkv_plan {
+    int64_t kernel, pairs, nw, cpw, wg_threads, rows_per_tile, tiles, grid_x, grid_y, launches, band_tiles,
+        last_grid_x, work_loop, units, fields_per_block, partial_slots, partial_cols;
+} nkv_plan;
+int nkv_stream_plan(const nkv_layout* L, int op, int j, unsigned flags, nkv_plan* plan);
+
 /* ---- synthetic operators (the matvec boundary, linear_operators.f90:17-23) ----------------
  * op_diag: y = d .* x over every stored row; y.time = time_scale * x.time.
  * op_rot2: per weighted point i, (u,v) = (wf_0[i], wf_1[i]):

@@ -24,6 +24,10 @@ NKV_ROT_MAX_OUT = 256   # most output columns of a basis rotation with more than
 NKV_GS_MAX_FIELDS = 64   # most field segments per gather-scatter launch (include/nekkrylov.h)
 # the kernel family nkv_rotate_plan reports (include/nekkrylov.h)
 NKV_ROT_PATH_FEW, NKV_ROT_PATH_WIDE, NKV_ROT_PATH_STREAM, NKV_ROT_PATH_CHUNKED = 1, 2, 3, 4
+# the entry points nkv_stream_plan knows (its op; the plan's kernel is the op or NKV_STREAM_SPLIT) and its work loops
+(NKV_STREAM_BLOCK_DOT, NKV_STREAM_BLOCK_UPDATE, NKV_STREAM_UPDATE_DOT, NKV_STREAM_BLOCK_DOT2, NKV_STREAM_DCGS2_UPDATE,
+ NKV_STREAM_AXPY_DOT, NKV_STREAM_BLAS1, NKV_STREAM_OP_DIAG, NKV_STREAM_FINISH, NKV_STREAM_SPLIT) = range(1, 11)
+NKV_STREAM_LOOP_TILES, NKV_STREAM_LOOP_UNITS = 1, 2
 NKV_OK, NKV_EINVAL, NKV_EHIP, NKV_ENAN, NKV_ESHAPE, NKV_ECALLBACK, NKV_EBREAKDOWN = 0, 1, 2, 3, 4, 5, 6
 NKV_TIME = 0x1
 NKV_ACCUMULATE = 0x2
@@ -72,6 +76,14 @@ class nkv_layout(Structure):
     ]
 
 
+class nkv_plan(Structure):
+    """What nkv_stream_plan fills (include/nekkrylov.h)."""
+
+    _fields_ = [(name, c_int64) for name in (
+        "kernel", "pairs", "nw", "cpw", "wg_threads", "rows_per_tile", "tiles", "grid_x", "grid_y", "launches",
+        "band_tiles", "last_grid_x", "work_loop", "units", "fields_per_block", "partial_slots", "partial_cols")]
+
+
 _P = c_void_p  # device pointers and streams travel as plain addresses
 _L = POINTER(nkv_layout)
 # callbacks of nkv_arnoldi_dcgs2: matvec(user, x, y, stream), allreduce(user, buf, n, stream)
@@ -118,6 +130,7 @@ _SIGNATURES = {
     "nkv_rotate_cols": (c_int, [_L, _P, c_int, _P, c_int, c_int, _P]),
     "nkv_rotate_plan": (c_int, [_L, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                 POINTER(c_int)]),
+    "nkv_stream_plan": (c_int, [_L, c_int, c_int, c_uint, POINTER(nkv_plan)]),
     "nkv_op_diag": (c_int, [_L, _P, _P, _P, c_double, _P]),
     "nkv_op_rot2": (c_int, [_L, _P, _P, _P, _P, _P, c_int, _P]),
     "nkv_op_cdiag": (c_int, [_L, _P, _P, _P, _P, c_int, _P]),

@@ -91,8 +91,6 @@ __global__ __launch_bounds__(kThreads) void k_block_update(const double* __restr
 // then feed the second projection, accumulated per lane across all tiles of the workgroup and
 // reduced across lanes once at the end.
 // ------------------------------------------------------------------------------------------
-constexpr int kFuseRows = 128;
-
 template <int NW, int CPW>
 __global__ __launch_bounds__(NW * 64) void k_update_dot(const double* __restrict__ Q, int64_t ld, int j,
                                                          const double* __restrict__ h,
@@ -654,46 +652,30 @@ void k_dcgs2_update(const double* __restrict__ Q, int64_t ld, int m,
     if (threadIdx.x == 0) partials[blockIdx.x] = nrm;
 }
 
+// The launches of nkv_stream_plan(NKV_STREAM_BLOCK_UPDATE): one per row band (the first band launches the
+// whole grid, so every block's partial slot is written before a later band adds to it; the time slot is
+// updated in the first band only).
 template <int P>
-int launch_block_update_p(const nkv_layout* L, const double* w, const double* Q, int j, const double* h_dev,
-                          double* f, double* part, unsigned flags, hipStream_t st, int* g_out) {
-    constexpr int kTile = kThreads * P * 2;
+int launch_block_update_p(const nkv_layout* L, const nkv_plan& p, const double* w, const double* Q, int j,
+                          const double* h_dev, double* f, double* part, unsigned flags, hipStream_t st) {
     const bool over = (flags & NKV_OVERWRITE) != 0;
     const bool norm = (flags & NKV_NORM2) != 0;
-    const int tpf = (int)(L->sv / kTile);
+    const int tpf = (int)(L->sv / p.rows_per_tile);
     const int tiles_w = tpf * L->n_wf;
-    const int tiles_total = (int)(rows_of(L) / kTile);
-    // few columns: a 4x larger grid (the norm partials still fit: the workspace holds at least
-    // 4 * kMaxBlocks slots, nkv_workspace_bytes with max_cols >= 1)
-    const int gmax = j <= NKV_UPD_SMALL_J ? 4 * kMaxBlocks : kMaxBlocks;
-    int g = tiles_total < gmax ? tiles_total : gmax;
-    if (g < 1) g = 1;
-    *g_out = g;
+    const int tiles_total = (int)p.tiles;
     const int64_t T = rows_of(L);
     const int dt = (flags & NKV_TIME) ? 1 : 0;
     auto kern = over ? (norm ? k_block_update<true, true, P> : k_block_update<true, false, P>)
                      : (norm ? k_block_update<false, true, P> : k_block_update<false, false, P>);
-    // NKV_UPD_ROUNDS > 0: one launch per row band of that many grid-stride rounds, as the DCGS2
-    // updates (the first band launches the whole grid, so every block's partial slot is written)
-    const int64_t b = (int64_t)NKV_UPD_ROUNDS * g;
-    const int band = (NKV_UPD_ROUNDS <= 0 || b >= tiles_total || tiles_total < 2 * b) ? (tiles_total > 0 ? tiles_total : 1)
-                                                                                        : (int)b;
-    for (int lo = 0; lo == 0 || lo < tiles_total; lo += band) {
-        const int hi = lo + band < tiles_total ? lo + band : tiles_total;
-        const int gb = lo == 0 ? g : (g < hi - lo ? g : hi - lo);
-        hipLaunchKernelGGL(kern, dim3(gb), dim3(kThreads), 0, st, Q, L->ld, j, h_dev, f, w, L->sv, tpf, tiles_w, hi, T,
-                           lo == 0 ? dt : 0, part, lo, lo == 0 ? 0 : 1);
+    for (int64_t i = 0; i < p.launches; ++i) {
+        const int lo = (int)(i * p.band_tiles);
+        const int hi = lo + p.band_tiles < tiles_total ? (int)(lo + p.band_tiles) : tiles_total;
+        const int64_t gb = i + 1 == p.launches ? p.last_grid_x : p.grid_x;
+        hipLaunchKernelGGL(kern, dim3((unsigned)gb), dim3(kThreads), 0, st, Q, L->ld, j, h_dev, f, w, L->sv, tpf, tiles_w,
+                           hi, T, lo == 0 ? dt : 0, part, lo, lo == 0 ? 0 : 1);
         NKV_LAUNCHED();
     }
     return NKV_OK;
-}
-
-// Tiles per launch of a banded update (NKV_DC_ROUNDS grid-stride rounds of a g-block grid); all
-// tiles in one launch when banding is off or the vector is shorter than two bands.
-inline int band_tiles(int tiles_total, int g) {
-    if (NKV_DC_ROUNDS <= 0) return tiles_total > 0 ? tiles_total : 1;
-    const int64_t b = (int64_t)NKV_DC_ROUNDS * g;
-    return (b >= tiles_total || tiles_total < 2 * b) ? (tiles_total > 0 ? tiles_total : 1) : (int)b;
 }
 
 // MGS pass coefficients in inverse compact WY form: see nkv_mgs_icwy_solve.
@@ -731,7 +713,8 @@ int nkv_block_update(const nkv_layout* L, const double* w, const double* Q, int 
     CHECK(check_ptr(Q, "Q"));
     CHECK(check_ptr(f, "f"));
     if (!h_dev) return fail(NKV_EINVAL, "h_dev is NULL");
-    if (j < 0) return fail(NKV_EINVAL, "j=%d < 0", j);
+    nkv_plan p;   // refuses j < 0
+    CHECK(nkv_stream_plan(L, NKV_STREAM_BLOCK_UPDATE, j, flags, &p));
     const bool norm = (flags & NKV_NORM2) != 0;
     if (norm) {
         CHECK(check_ptr(w, "w"));
@@ -740,10 +723,10 @@ int nkv_block_update(const nkv_layout* L, const double* w, const double* Q, int 
     }
     double* part = ws ? partials_of(ws) : nullptr;
     hipStream_t st = S(stream);
-    int g = 1;
+    const int g = (int)p.grid_x;
     const int64_t T = rows_of(L);
-    if (use_large_tiles(L)) CHECK(launch_block_update_p<NKV_PAIRS>(L, w, Q, j, h_dev, f, part, flags, st, &g));
-    else CHECK(launch_block_update_p<NKV_PAIRS_SMALL>(L, w, Q, j, h_dev, f, part, flags, st, &g));
+    if (p.pairs == NKV_PAIRS) CHECK(launch_block_update_p<NKV_PAIRS>(L, p, w, Q, j, h_dev, f, part, flags, st));
+    else CHECK(launch_block_update_p<NKV_PAIRS_SMALL>(L, p, w, Q, j, h_dev, f, part, flags, st));
     if (norm) {
         // ||f||^2 time term (NKV_TIME_DOT: uparam(1)==2.1 / real_dot) only on the rank owning the
         // replicated scalar.  NKV_TIME alone updates the slot but keeps it out of the norm (k_norm
@@ -762,49 +745,42 @@ int nkv_block_update_dot(const nkv_layout* L, const double* w, const double* Q, 
     CHECK(check_ptr(f, "f"));
     CHECK(check_ptr(ws, "ws"));
     if (!h_dev || !hout_dev) return fail(NKV_EINVAL, "h_dev/hout_dev is NULL");
-    if (j < 1 || j > NKV_MAX_COLS) return fail(NKV_EINVAL, "j=%d outside 1..%d", j, NKV_MAX_COLS);
+    nkv_plan p;   // refuses j outside 1..NKV_MAX_COLS
+    CHECK(nkv_stream_plan(L, NKV_STREAM_UPDATE_DOT, j, flags, &p));
     const unsigned upd_flags = (flags & NKV_TIME) ? NKV_TIME : 0u;
     const unsigned dot_flags = (flags & NKV_TIME_DOT) ? NKV_TIME : 0u;
-    if (j > 256 || rows_of(L) >= (int64_t)1 << 29) {  // tile does not fit registers / 32-bit offsets
+    if (p.kernel == NKV_STREAM_SPLIT) {  // tile does not fit registers / 32-bit offsets
         CHECK(nkv_block_update(L, w, Q, j, h_dev, f, nullptr, ws, upd_flags, stream));
         return launch_block_dot(L, w, Q, L->ld, j, f, hout_dev, ws, dot_flags, S(stream));
     }
-    const int64_t rows = rows_of(L);
-    const int64_t tiles_total = rows / kFuseRows;
+    const int64_t tiles_total = p.tiles;
     const int64_t tpf = L->sv / kFuseRows;
     const int64_t tiles_w = tpf * L->n_wf;
-    // mid-size column counts run the fused pass on a smaller grid (NKV_FUSE_G_MID workgroups for
-    // NKV_FUSE_MID_LO <= j <= NKV_FUSE_MID_HI)
-    const int64_t gcap = (j >= NKV_FUSE_MID_LO && j <= NKV_FUSE_MID_HI) ? NKV_FUSE_G_MID : NKV_FUSE_G;
-    int64_t g = tiles_total < gcap ? tiles_total : gcap;
-    if (g < 1) g = 1;
-    const int B = (int)g;
-    const int64_t T = rows;
+    const int B = (int)p.partial_slots;
+    const int64_t T = rows_of(L);
     const int dt = (flags & NKV_TIME) ? 1 : 0;
     double* part = partials_of(ws);
     hipStream_t st = S(stream);
-    // NKV_FUSE_ROUNDS > 0: one launch per row band of that many grid-stride rounds (the first band
-    // launches the whole grid, so every partial slot is written before later bands add to it)
-    const int64_t fb = (int64_t)NKV_FUSE_ROUNDS * g;
-    const int64_t fband = (NKV_FUSE_ROUNDS <= 0 || fb >= tiles_total || tiles_total < 2 * fb)
-                              ? (tiles_total > 0 ? tiles_total : 1) : fb;   // >= 1: an empty shard launches once
+    // one launch per row band of the plan (the first band launches the whole grid, so every partial slot is
+    // written before later bands add to it); an empty shard launches once
 #define NKV_FUSE(NW, CPW)                                                                                        \
-    for (int64_t lo = 0; lo == 0 || lo < tiles_total; lo += fband) {                                             \
-        const int64_t hi = lo + fband < tiles_total ? lo + fband : tiles_total;                                  \
-        const int64_t gb = lo == 0 ? g : (g < hi - lo ? g : hi - lo);                                            \
+    for (int64_t i = 0; i < p.launches; ++i) {                                                                   \
+        const int64_t lo = i * p.band_tiles;                                                                     \
+        const int64_t hi = lo + p.band_tiles < tiles_total ? lo + p.band_tiles : tiles_total;                    \
+        const int64_t gb = i + 1 == p.launches ? p.last_grid_x : p.grid_x;                                       \
         hipLaunchKernelGGL((k_update_dot<NW, CPW>), dim3((unsigned)gb), dim3(NW * 64), 0, st, Q, L->ld, j, h_dev, f, \
                            w, L->sv, tpf, tiles_w, hi, T, lo == 0 ? dt : 0, part, B, lo, lo == 0 ? 0 : 1);        \
     }
     constexpr int NW = NKV_FUSE_NW;
-    const int cpw = j <= NW * 16 ? (j + NW - 1) / NW : (j + 15) / 16;
-    if (j <= NKV_FUSE_SMALL_J) {   // few columns: 4 waves per workgroup (+4 % at j = 8, +28 % at j = 2)
-        switch ((j + 3) / 4) {
+    const int cpw = (int)p.cpw;
+    if (p.nw == 4 && NW != 4) {   // few columns: 4 waves per workgroup (+4 % at j = 8, +28 % at j = 2)
+        switch (cpw) {
             case 1: NKV_FUSE(4, 1); break;
             case 2: NKV_FUSE(4, 2); break;
             case 3: NKV_FUSE(4, 3); break;
             default: NKV_FUSE(4, 4); break;
         }
-    } else if (j <= NW * 16) {
+    } else if (p.nw == NW) {
         switch (cpw) {
             case 1: NKV_FUSE(NW, 1); break;
             case 2: NKV_FUSE(NW, 2); break;
@@ -851,38 +827,23 @@ int nkv_block_dot2(const nkv_layout* L, const double* w, const double* Q, int j,
     CHECK(check_ptr(y, "y"));
     CHECK(check_ptr(ws, "ws"));
     if (!h_dev) return fail(NKV_EINVAL, "h_dev is NULL");
-    if (j < 1 || j > NKV_MAX_COLS) return fail(NKV_EINVAL, "j=%d outside 1..%d", j, NKV_MAX_COLS);
+    nkv_plan p;   // refuses j outside 1..NKV_MAX_COLS
+    CHECK(nkv_stream_plan(L, NKV_STREAM_BLOCK_DOT2, j, flags, &p));
     if ((flags & NKV_X_IS_LAST) && x != Q + (int64_t)(j - 1) * L->ld)
         return fail(NKV_EINVAL, "NKV_X_IS_LAST: x is not column j-1 of Q");
     hipStream_t st = S(stream);
-    const bool large = use_large_tiles(L);
-    const int P = large ? NKV_D2_PAIRS : NKV_PAIRS_SMALL;
-    const int kTile = kThreads * P * 2;
-    const int tpf = (int)(L->sv / kTile);
-    // large problems: one block row walks every field of its tiles (weights read once per tile)
-    const int nf = (large && NKV_D2_FIELDLOOP) ? L->n_wf : 1;
-    const int gy = L->n_wf / nf;
-    // one workgroup per CU for large problems (8 rows/thread keep enough loads in flight); two per
-    // CU for small problems (4 rows/thread), each walking a few tiles
-    const int bmax = large ? NKV_D2_MAXB : NKV_D2_SMALL_B;
-    int bx = (bmax < kMaxBlocks ? bmax : kMaxBlocks) / gy;
-    if (bx > tpf) bx = tpf;
-    if (bx < 1) bx = 1;
-    const int B = bx * gy;
+    const int B = (int)p.partial_slots;
     double* part = partials_of(ws);
-    if (tpf > 0) {
+    if (p.launches > 0) {
         const int xl = (flags & NKV_X_IS_LAST) ? 1 : 0;
-        if (large)
-            hipLaunchKernelGGL(k_block_dot2<NKV_D2_PAIRS>, dim3(bx, gy), dim3(kThreads), 8 * j * sizeof(double), st,
-                               Q, L->ld, j, x, y, w, L->sv, tpf, nf, xl, part, B);
-        else
-            hipLaunchKernelGGL(k_block_dot2<NKV_PAIRS_SMALL>, dim3(bx, gy), dim3(kThreads), 8 * j * sizeof(double),
-                               st, Q, L->ld, j, x, y, w, L->sv, tpf, nf, xl, part, B);
+        auto kern = p.pairs == NKV_D2_PAIRS ? k_block_dot2<NKV_D2_PAIRS> : k_block_dot2<NKV_PAIRS_SMALL>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(kThreads), 8 * j * sizeof(double), st,
+                           Q, L->ld, j, x, y, w, L->sv, (int)p.tiles, (int)p.fields_per_block, xl, part, B);
         NKV_LAUNCHED();
     }
     const int64_t T = rows_of(L);
     const bool tdot = (flags & NKV_TIME) && L->rank0;
-    CHECK(launch_reduce_cols(2 * j, part, tpf > 0 ? B : 0, h_dev, tdot ? Q + T : nullptr, L->ld, tdot ? x + T : nullptr, tdot ? y + T : nullptr, j, nan_flag_of(ws), st));
+    CHECK(launch_reduce_cols(2 * j, part, B, h_dev, tdot ? Q + T : nullptr, L->ld, tdot ? x + T : nullptr, tdot ? y + T : nullptr, j, nan_flag_of(ws), st));
     return NKV_OK;
 }
 
@@ -936,40 +897,32 @@ int nkv_dcgs2_update(const nkv_layout* L, const double* w, const double* Q, int 
     CHECK(check_ptr(win, "win"));
     CHECK(check_ptr(fout, "fout"));
     CHECK(check_ptr(ws, "ws"));
-    if (m < 0) return fail(NKV_EINVAL, "m=%d < 0", m);
+    nkv_plan p;   // refuses m < 0
+    CHECK(nkv_stream_plan(L, NKV_STREAM_DCGS2_UPDATE, m, nrm2_dev ? NKV_NORM2 : 0u, &p));
     if (!coef_dev) return fail(NKV_EINVAL, "coef is NULL");
     hipStream_t st = S(stream);
-    const bool large = use_large_tiles(L);
-    const int P = large ? NKV_DC_PAIRS : NKV_PAIRS_SMALL;
-    const int kTile = kThreads * P * 2;
-    const int tpf = (int)(L->sv / kTile);
+    const bool large = p.pairs == NKV_DC_PAIRS;
+    const int tpf = (int)(L->sv / p.rows_per_tile);
     const int tiles_w = tpf * L->n_wf;
-    const int tiles_total = (int)(rows_of(L) / kTile);
-    const int gmax = NKV_DC_G < kMaxBlocks ? NKV_DC_G : kMaxBlocks;
-    int g = tiles_total < gmax ? tiles_total : gmax;
-    if (g < 1) g = 1;
+    const int tiles_total = (int)p.tiles;
+    const int g = (int)p.grid_x;
     const int64_t T = rows_of(L);
     const int dt = (flags & NKV_TIME) ? 1 : 0;
     double* part = partials_of(ws);
     auto kern = large ? (nrm2_dev ? k_dcgs2_update<NKV_DC_PAIRS, true> : k_dcgs2_update<NKV_DC_PAIRS, false>)
                       : (nrm2_dev ? k_dcgs2_update<NKV_PAIRS_SMALL, true> : k_dcgs2_update<NKV_PAIRS_SMALL, false>);
-    if (!nrm2_dev) {
-        // one launch per row band of NKV_DC_ROUNDS grid-stride rounds: every launch boundary is a
-        // grid-wide point where all loads and stores of the band have retired (no in-kernel barrier)
-        const int band = band_tiles(tiles_total, g);
-        for (int lo = 0; lo == 0 || lo < tiles_total; lo += band) {   // >= 1 launch: also the time slot
-            const int hi = lo + band < tiles_total ? lo + band : tiles_total;
-            const int gb = g < hi - lo ? g : (hi - lo > 0 ? hi - lo : 1);
-            hipLaunchKernelGGL(kern, dim3(gb), dim3(kThreads), 0, st, Q, L->ld, m, coef_dev, qj, win, fout, w, L->sv,
-                               tpf, tiles_w, tiles_total, T, lo == 0 ? dt : 0, part, lo, hi);
-            NKV_LAUNCHED();
-        }
-        return NKV_OK;
+    // without norm: one launch per row band (every launch boundary is a grid-wide point where all loads and
+    // stores of the band have retired, no in-kernel barrier).  With the fused norm every block leaves one
+    // partial: a single launch over all tiles.  At least one launch either way: also the time slot
+    for (int64_t i = 0; i < p.launches; ++i) {
+        const int lo = (int)(i * p.band_tiles);
+        const int hi = lo + p.band_tiles < tiles_total ? (int)(lo + p.band_tiles) : tiles_total;
+        const int64_t gb = i + 1 == p.launches ? p.last_grid_x : p.grid_x;
+        hipLaunchKernelGGL(kern, dim3((unsigned)gb), dim3(kThreads), 0, st, Q, L->ld, m, coef_dev, qj, win, fout, w, L->sv,
+                           tpf, tiles_w, tiles_total, T, lo == 0 ? dt : 0, part, lo, hi);
+        NKV_LAUNCHED();
     }
-    // with the fused norm every block leaves one partial: a single launch over all tiles
-    hipLaunchKernelGGL(kern, dim3(g), dim3(kThreads), 0, st, Q, L->ld, m, coef_dev, qj, win, fout, w, L->sv, tpf,
-                       tiles_w, tiles_total, T, dt, part, 0, tiles_total);
-    NKV_LAUNCHED();
+    if (!nrm2_dev) return NKV_OK;
     const bool tdot = (flags & NKV_TIME_DOT) && L->rank0;
     CHECK(launch_reduce_cols(1, part, g, nrm2_dev, tdot ? fout + T : nullptr, (int64_t)0, tdot ? fout + T : nullptr, nullptr, 1 << 30, nan_flag_of(ws), st));
     return NKV_OK;

@@ -206,6 +206,7 @@ static_assert(NKV_TILE % (kThreads * NKV_PAIRS_SMALL * 2) == 0, "kernel tile mus
 constexpr int kMaxBlocks = NKV_MAXB;                 // reduction partial slots per column
 constexpr int kColUnroll = NKV_COLU;                 // columns in flight per thread (block dot)
 constexpr size_t kCtrlBytes = 256;                   // control words at the head of the workspace
+constexpr int kFuseRows = 128;                       // rows per tile of the fused CGS2 middle pass (k_update_dot)
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

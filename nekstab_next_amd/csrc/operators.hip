@@ -123,13 +123,14 @@ int nkv_op_diag(const nkv_layout* L, const double* d, const double* x, double* y
     const int64_t rows = rows_of(L);
     // one launch per NKV_STREAM_ROUNDS grid-stride rounds (a row band): +5-7 % at N=1e8
     // (profiles/r02h_tune_bands_update_opdiag.log), as for the DCGS2 updates
-    const int g = grid_for(rows / 2);
-    const int64_t chunks = rows / (2 * kThreads * kStreamUnr);
-    const int64_t band = NKV_STREAM_ROUNDS > 0 && chunks >= 2 * (int64_t)NKV_STREAM_ROUNDS * g
-                             ? (int64_t)NKV_STREAM_ROUNDS * g : (chunks > 0 ? chunks : 1);
-    for (int64_t lo = 0; lo == 0 || lo < chunks; lo += band) {
-        const int64_t hi = lo + band < chunks ? lo + band : chunks;
-        hipLaunchKernelGGL(k_op_diag, dim3(g), dim3(kThreads), 0, S(stream), d, x, y, rows, time_scale, lo, hi);
+    // (nkv_stream_plan holds the band rule)
+    nkv_plan p;
+    CHECK(nkv_stream_plan(L, NKV_STREAM_OP_DIAG, 0, 0u, &p));
+    const int64_t chunks = p.tiles;
+    for (int64_t i = 0; i < p.launches; ++i) {
+        const int64_t lo = i * p.band_tiles;
+        const int64_t hi = lo + p.band_tiles < chunks ? lo + p.band_tiles : chunks;
+        hipLaunchKernelGGL(k_op_diag, dim3((unsigned)p.grid_x), dim3(kThreads), 0, S(stream), d, x, y, rows, time_scale, lo, hi);
         NKV_LAUNCHED();
     }
     return NKV_OK;

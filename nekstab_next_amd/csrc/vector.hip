@@ -244,26 +244,14 @@ __global__ void k_accumulate(double* __restrict__ dst, const double* __restrict_
     if (threadIdx.x == 0) dst[0] += src[0];
 }
 
-template <int P>
-int launch_block_dot_p(const nkv_layout* L, const double* w, const double* Q, int64_t ld, int j,
-                       const double* f, double* out, void* ws, unsigned flags, hipStream_t st) {
-    constexpr int kTile = kThreads * P * 2;
-    const int tpf = (int)(L->sv / kTile);
-    const int bmax = (P == NKV_PAIRS_SMALL && P != NKV_PAIRS && NKV_DOT_SMALL_B < kMaxBlocks) ? NKV_DOT_SMALL_B : kMaxBlocks;
-    int bx = bmax / L->n_wf;
-    if (bx > tpf) bx = tpf;
-    if (bx < 1) bx = 1;
-    const int B = bx * L->n_wf;
-    double* part = partials_of(ws);
-    if (tpf > 0) {
-        hipLaunchKernelGGL(k_block_dot<P>, dim3(bx, L->n_wf), dim3(kThreads), 4 * j * sizeof(double), st,
-                           Q, ld, j, f, w, L->sv, tpf, part, B);
-        NKV_LAUNCHED();
-    }
-    const int64_t T = rows_of(L);
-    const bool tdot = (flags & NKV_TIME) && L->rank0;
-    hipLaunchKernelGGL(k_reduce_cols, dim3(j), dim3(kThreads), 0, st, part, tpf > 0 ? B : 0, out,
-                       tdot ? Q + T : nullptr, ld, tdot ? f + T : nullptr, nullptr, 1 << 30, nan_flag_of(ws));
+// k_finish on the grid nkv_stream_plan(NKV_STREAM_FINISH) reports.
+int launch_finish(const nkv_layout* L, const double* f, const double* nrm2, double* q, int j, const double* h1,
+                  const double* h2, double* hcol, double* beta_out, hipStream_t st) {
+    nkv_plan p;
+    CHECK(nkv_stream_plan(L, NKV_STREAM_FINISH, 0, 0u, &p));
+    const int64_t rows = rows_of(L);
+    hipLaunchKernelGGL(k_finish, dim3((unsigned)p.grid_x), dim3(kThreads), 0, st, f, nrm2, q, rows, rows, j, h1, h2,
+                       hcol, beta_out);
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -272,11 +260,24 @@ int launch_block_dot_p(const nkv_layout* L, const double* w, const double* Q, in
 
 namespace nkvi {
 
-// Shared launcher for block dots (nkv_dot is the j = 1 case).
+// Shared launcher for block dots (nkv_dot is the j = 1 case): the shape is nkv_stream_plan's.
 int launch_block_dot(const nkv_layout* L, const double* w, const double* Q, int64_t ld, int j,
                      const double* f, double* out, void* ws, unsigned flags, hipStream_t st) {
-    return use_large_tiles(L) ? launch_block_dot_p<NKV_PAIRS>(L, w, Q, ld, j, f, out, ws, flags, st)
-                              : launch_block_dot_p<NKV_PAIRS_SMALL>(L, w, Q, ld, j, f, out, ws, flags, st);
+    nkv_plan p;
+    CHECK(nkv_stream_plan(L, NKV_STREAM_BLOCK_DOT, j, flags, &p));
+    double* part = partials_of(ws);
+    if (p.launches > 0) {
+        auto kern = p.pairs == NKV_PAIRS ? k_block_dot<NKV_PAIRS> : k_block_dot<NKV_PAIRS_SMALL>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(kThreads), 4 * j * sizeof(double), st,
+                           Q, ld, j, f, w, L->sv, (int)p.tiles, part, (int)p.partial_slots);
+        NKV_LAUNCHED();
+    }
+    const int64_t T = rows_of(L);
+    const bool tdot = (flags & NKV_TIME) && L->rank0;
+    hipLaunchKernelGGL(k_reduce_cols, dim3(j), dim3(kThreads), 0, st, part, (int)p.partial_slots, out,
+                       tdot ? Q + T : nullptr, ld, tdot ? f + T : nullptr, nullptr, 1 << 30, nan_flag_of(ws));
+    NKV_LAUNCHED();
+    return NKV_OK;
 }
 
 int launch_reduce_cols(int ncols, const double* partials, int B, double* out, const double* ta, int64_t lda,
@@ -296,7 +297,9 @@ static int blas1(const nkv_layout* L, int op, double* x, const double* y, const 
     CHECK(check_layout(L));
     CHECK(check_ptr(x, "x"));
     const int64_t rows = rows_of(L);
-    const int g = grid_for(rows / 2 + 1);
+    nkv_plan p;
+    CHECK(nkv_stream_plan(L, NKV_STREAM_BLAS1, 0, 0u, &p));
+    const unsigned g = (unsigned)p.grid_x;
     const int dt = (flags & NKV_TIME) ? 1 : 0;
     hipStream_t st = S(stream);
     switch (op) {
@@ -346,11 +349,7 @@ int nkv_normalize_dev(const nkv_layout* L, double* x, const double* nrm2_dev, do
     CHECK(check_layout(L));
     CHECK(check_ptr(x, "x"));
     if (!nrm2_dev) return fail(NKV_EINVAL, "nrm2_dev is NULL");
-    const int64_t rows = rows_of(L);
-    hipLaunchKernelGGL(k_finish, dim3(grid_for(rows / 2)), dim3(kThreads), 0, S(stream), x, nrm2_dev,
-                       x, rows, rows, 0, nullptr, nullptr, nullptr, beta_dev);
-    NKV_LAUNCHED();
-    return NKV_OK;
+    return launch_finish(L, x, nrm2_dev, x, 0, nullptr, nullptr, nullptr, beta_dev, S(stream));
 }
 
 int nkv_dot(const nkv_layout* L, const double* w, const double* a, const double* b, double* out_dev,
@@ -385,11 +384,7 @@ int nkv_arnoldi_finish(const nkv_layout* L, const double* f, const double* nrm2_
     CHECK(check_ptr(q_out, "q_out"));
     if (!nrm2_dev) return fail(NKV_EINVAL, "nrm2_dev is NULL");
     if (hcol_dev && (!h1_dev || j < 0)) return fail(NKV_EINVAL, "hcol needs h1 and j >= 0");
-    const int64_t rows = rows_of(L);
-    hipLaunchKernelGGL(k_finish, dim3(grid_for(rows / 2)), dim3(kThreads), 0, S(stream), f, nrm2_dev,
-                       q_out, rows, rows, j, h1_dev, h2_dev, hcol_dev, nullptr);
-    NKV_LAUNCHED();
-    return NKV_OK;
+    return launch_finish(L, f, nrm2_dev, q_out, j, h1_dev, h2_dev, hcol_dev, nullptr, S(stream));
 }
 
 int nkv_normalize_store(const nkv_layout* L, const double* f, const double* nrm2_dev, double* q_next,
@@ -399,11 +394,7 @@ int nkv_normalize_store(const nkv_layout* L, const double* f, const double* nrm2
     CHECK(check_ptr(f, "f"));
     CHECK(check_ptr(q_next, "q_next"));
     if (!nrm2_dev) return fail(NKV_EINVAL, "nrm2_dev is NULL");
-    const int64_t rows = rows_of(L);
-    hipLaunchKernelGGL(k_finish, dim3(grid_for(rows / 2)), dim3(kThreads), 0, S(stream), f, nrm2_dev, q_next, rows,
-                       rows, 0, nullptr, nullptr, nullptr, beta_dev);
-    NKV_LAUNCHED();
-    return NKV_OK;
+    return launch_finish(L, f, nrm2_dev, q_next, 0, nullptr, nullptr, nullptr, beta_dev, S(stream));
 }
 
 int nkv_axpy_dot(const nkv_layout* L, const double* w, double* f, const double* alpha_dev, const double* qa,
@@ -415,34 +406,27 @@ int nkv_axpy_dot(const nkv_layout* L, const double* w, double* f, const double* 
     CHECK(check_ptr(ws, "ws"));
     if (!alpha_dev || !out_dev) return fail(NKV_EINVAL, "alpha_dev/out_dev is NULL");
     if (qb) CHECK(check_ptr(qb, "qb"));
-    // 4 double2 per thread at every size: +5 % over the 8 of the wide kernels at N=1e8 for this
-    // four-stream shape (profiles/r02bl_tune_fewcol.log)
-    constexpr int P = NKV_PAIRS_SMALL;
-    const int kTile = kThreads * P * 2;
-    const int tpf = (int)(L->sv / kTile);
+    nkv_plan p;   // always k_axpy_dot<NKV_PAIRS_SMALL>; bands (first band: whole grid) only with NKV_AXD_ROUNDS > 0
+    CHECK(nkv_stream_plan(L, NKV_STREAM_AXPY_DOT, 1, flags, &p));
+    const int tpf = (int)(L->sv / p.rows_per_tile);
     const int tiles_w = tpf * L->n_wf;
-    const int tiles_total = (int)(rows_of(L) / kTile);
-    int g = tiles_total < kMaxBlocks ? tiles_total : kMaxBlocks;
-    if (g < 1) g = 1;
+    const int tiles_total = (int)p.tiles;
     const int64_t T = rows_of(L);
     const int dt = (flags & NKV_TIME) ? 1 : 0;
     double* part = partials_of(ws);
     hipStream_t st = S(stream);
-    auto kern = k_axpy_dot<P>;
-    // NKV_AXD_ROUNDS > 0: one launch per row band of that many grid-stride rounds (first band: whole grid)
-    const int64_t b = (int64_t)NKV_AXD_ROUNDS * g;
-    const int band = (NKV_AXD_ROUNDS <= 0 || b >= tiles_total || tiles_total < 2 * b) ? (tiles_total > 0 ? tiles_total : 1)
-                                                                                        : (int)b;
-    for (int lo = 0; lo == 0 || lo < tiles_total; lo += band) {
-        const int hi = lo + band < tiles_total ? lo + band : tiles_total;
-        const int gb = lo == 0 ? g : (g < hi - lo ? g : hi - lo);
-        hipLaunchKernelGGL(kern, dim3(gb), dim3(kThreads), 0, st, qa, alpha_dev, f, qb, w, L->sv, tpf, tiles_w, hi, T,
-                           lo == 0 ? dt : 0, part, lo, lo == 0 ? 0 : 1);
+    auto kern = k_axpy_dot<NKV_PAIRS_SMALL>;
+    for (int64_t i = 0; i < p.launches; ++i) {
+        const int lo = (int)(i * p.band_tiles);
+        const int hi = lo + p.band_tiles < tiles_total ? (int)(lo + p.band_tiles) : tiles_total;
+        const int64_t gb = i + 1 == p.launches ? p.last_grid_x : p.grid_x;
+        hipLaunchKernelGGL(kern, dim3((unsigned)gb), dim3(kThreads), 0, st, qa, alpha_dev, f, qb, w, L->sv, tpf, tiles_w, hi,
+                           T, lo == 0 ? dt : 0, part, lo, lo == 0 ? 0 : 1);
         NKV_LAUNCHED();
     }
     const bool tdot = (flags & NKV_TIME_DOT) && L->rank0;   // the replicated time product, once
     const double* tq = qb ? qb : f;
-    hipLaunchKernelGGL(k_reduce_cols, dim3(1), dim3(kThreads), 0, st, part, tiles_total > 0 ? g : 0, out_dev,
+    hipLaunchKernelGGL(k_reduce_cols, dim3(1), dim3(kThreads), 0, st, part, (int)p.partial_slots, out_dev,
                        tdot ? tq + T : nullptr, (int64_t)0, tdot ? f + T : nullptr, nullptr, 1 << 30, nan_flag_of(ws));
     NKV_LAUNCHED();
     return NKV_OK;
@@ -480,11 +464,7 @@ int nkv_mgs2_step(const nkv_layout* L, const double* w, const double* Q, int j, 
         }
     }
     if (j == 0) CHECK(nkv_dot(L, w, f, f, tmp + 1, ws, tdot, st));          // ||f||^2
-    const int64_t rows = rows_of(L);                                          // q_out = f/||f||, H(k+1,k)
-    hipLaunchKernelGGL(k_finish, dim3(grid_for(rows / 2)), dim3(kThreads), 0, st, f, tmp + 1, q_out, rows, rows, 0,
-                       nullptr, nullptr, nullptr, hcol_dev + j);
-    NKV_LAUNCHED();
-    return NKV_OK;
+    return launch_finish(L, f, tmp + 1, q_out, 0, nullptr, nullptr, nullptr, hcol_dev + j, st);   // q_out = f/||f||, H(k+1,k)
 }
 
 }  // extern "C"

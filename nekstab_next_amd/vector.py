@@ -360,8 +360,39 @@ def rotate_plan(layout, k: int, n_out: int, ldv: int | None = None) -> tuple[str
     return ROTATE_PATHS[out[0].value], out[1].value, out[2].value, out[3].value
 
 
+STREAM_OPS = {"block_dot": _lib.NKV_STREAM_BLOCK_DOT, "block_update": _lib.NKV_STREAM_BLOCK_UPDATE,
+              "update_dot": _lib.NKV_STREAM_UPDATE_DOT, "block_dot2": _lib.NKV_STREAM_BLOCK_DOT2,
+              "dcgs2_update": _lib.NKV_STREAM_DCGS2_UPDATE, "axpy_dot": _lib.NKV_STREAM_AXPY_DOT,
+              "blas1": _lib.NKV_STREAM_BLAS1, "op_diag": _lib.NKV_STREAM_OP_DIAG, "finish": _lib.NKV_STREAM_FINISH}
+_STREAM_KERNELS = {**{v: k for k, v in STREAM_OPS.items()}, _lib.NKV_STREAM_SPLIT: "split"}
+_STREAM_LOOPS = {0: None, _lib.NKV_STREAM_LOOP_TILES: "tiles", _lib.NKV_STREAM_LOOP_UNITS: "units"}
+
+
+class StreamPlan(dict):
+    """The fields of ``nkv_plan`` as a dict with attribute access (``kernel`` and ``work_loop`` as names)."""
+
+    __getattr__ = dict.__getitem__
+
+
+def stream_plan(layout, op: str, j: int = 1, flags: int = 0) -> StreamPlan:
+    """The launch shape of a streaming entry point for ``(layout, op, j, flags)``, from the library's own
+    dispatch (``nkv_stream_plan``, host only: no GPU needed).  ``op``: a key of ``STREAM_OPS``; ``j``: the
+    columns of the call (``m`` for the DCGS2 update); ``flags``: ``NKV_NORM2`` (for the DCGS2 update:
+    ``nrm2_dev`` given), ``NKV_OVERWRITE``, ``NKV_X_IS_LAST``.  ``kernel`` is the op's name, or "split" where
+    ``nkv_block_update_dot`` runs a block update and a block dot; the other fields: include/nekkrylov.h."""
+    L = layout.c_struct() if isinstance(layout, NekLayout) else layout
+    p = _lib.nkv_plan()
+    _lib.check(_lib.load().nkv_stream_plan(ctypes.byref(L), STREAM_OPS[op], int(j), int(flags), ctypes.byref(p)),
+               "nkv_stream_plan")
+    out = StreamPlan((name, int(getattr(p, name))) for name, _ in p._fields_)
+    out["kernel"] = _STREAM_KERNELS[out["kernel"]]
+    out["work_loop"] = _STREAM_LOOPS[out["work_loop"]]
+    return out
+
+
 __all__ = [
     "NekContext", "NekVector", "ComplexNekVector", "Basis", "k_dot", "k_norm", "k_normalize", "k_cmult",
     "k_add2", "k_sub2", "k_sub3", "k_zero", "k_copy", "k_matmul", "combine", "NKV_NORM2",
     "inner_product", "norm", "normalize", "rotate_plan", "ROTATE_PATHS",
+    "stream_plan", "STREAM_OPS", "StreamPlan",
 ]

@@ -13,11 +13,11 @@ import torch
 import oracle as orc
 from helpers import olayout
 from nekstab_next_amd import synthetic as syn
-from nekstab_next_amd._lib import NKV_NORM2, NKV_TIME, NkvError, NkvNaNError
+from nekstab_next_amd._lib import NKV_NORM2, NKV_OVERWRITE, NKV_TIME, NkvError, NkvNaNError
 from nekstab_next_amd.arnoldi import HessenbergDev, arnoldi_factorization
 from nekstab_next_amd.layout import NekLayout
 from nekstab_next_amd.operators import DiagOperator, Rot2Operator
-from nekstab_next_amd.vector import NekContext, k_matmul, k_normalize, rotate_plan
+from nekstab_next_amd.vector import NekContext, k_matmul, k_normalize, rotate_plan, stream_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -127,6 +127,13 @@ def test_dot_vs_oracle(gpu, name, time_in_dot):
 @pytest.mark.parametrize("j", [1, 3, 4, 5, 37, 128])
 def test_block_dot_update_vs_numpy(gpu, j):
     lay = LAYOUTS["2d"]
+    # one trip per workgroup: k_block_dot<4> on 6 tiles per field, k_block_update<*, *, 4> on 16 tiles (the later
+    # trips, the 8-pair tiles and the row bands: tests/test_gpu_stream_paths.py)
+    p = stream_plan(lay, "block_dot", j)
+    assert (p.pairs, p.tiles, p.grid_x, p.grid_y, p.launches) == (4, 6, 6, 2, 1), dict(p)
+    for flags in (NKV_NORM2, NKV_OVERWRITE):
+        p = stream_plan(lay, "block_update", j, flags)
+        assert (p.pairs, p.tiles, p.grid_x, p.launches) == (4, 16, 16, 1), dict(p)
     ctx, w = make_ctx(lay, max_cols=128)
     Q = ctx.basis(j + 1)
     for i in range(j):
@@ -545,6 +552,15 @@ def test_block_update_dot_fused_vs_numpy(gpu, j):
     """nkv_block_update_dot = update then weighted multi-dot, in one pass (all CPW variants +
     the two-pass fallback above 256 columns)."""
     lay = LAYOUTS["3d_scalar"]
+    # k_update_dot<NW, CPW> with one 128-row tile per workgroup (288 tiles on a grid of 288); a workgroup's second
+    # tile: tests/test_gpu_stream_paths.py
+    p = stream_plan(lay, "update_dot", j)
+    if j > 256:
+        assert p.kernel == "split", dict(p)
+    else:
+        nw_cpw = {1: (4, 1), 5: (4, 2), 8: (4, 2), 9: (4, 3), 31: (8, 4), 64: (8, 8), 65: (8, 9), 128: (8, 16),
+                  129: (16, 9), 200: (16, 13), 256: (16, 16)}[j]
+        assert (p.kernel, p.nw, p.cpw, p.tiles, p.grid_x, p.launches) == ("update_dot", *nw_cpw, 288, 288, 1), dict(p)
     ctx, w = make_ctx(lay, max_cols=300)
     Q = ctx.basis(j)
     for i in range(j):
@@ -801,9 +817,14 @@ def test_empty_shard(gpu):
 # ---- DCGS2 entry points, each against numpy on the same inputs (small- and large-tile paths) ----
 from nekstab_next_amd.layout import box3d_layout  # noqa: E402
 
-DC_LAYOUTS = {"small": LAYOUTS["3d_scalar"], "large": box3d_layout(4000),   # large: >= 2048 4096-row tiles
+# large: >= 2048 4096-row tiles (2211 and 2250), 500 and 750 per field.  With the norm, the DCGS2 update of both
+# large layouts runs its per-tile loop at m = 31 (fewer tiles per field than its 768 workgroups) and its per-unit
+# loop only at m < 8, with fewer units (711, 750) than workgroups; without, one launch (< 3072 tiles).  More units
+# than workgroups, the row bands and the other grid-stride loops: tests/test_gpu_stream_paths.py
+DC_LAYOUTS = {"small": LAYOUTS["3d_scalar"], "large": box3d_layout(4000),
               # large tiles with three weighted fields and no pressure segment (.not. ifpo)
               "large_3f_nopr": NekLayout(ldim=3, lx1=8, lx2=6, nelgv=6000, ifpo=False)}
+DC_TILES = {"small": (4, 18, 4), "large": (8, 2211, 500), "large_3f_nopr": (8, 2250, 750)}   # pairs, tiles, per field
 
 
 def _wfull(lay, w):
@@ -819,6 +840,12 @@ def _wfull(lay, w):
 def test_block_dot2_vs_numpy(gpu, name, j, x_last):
     from nekstab_next_amd._lib import NKV_X_IS_LAST
     lay = DC_LAYOUTS[name]
+    # small: k_block_dot2<4>, grid.y = the field, one tile per workgroup; large: k_block_dot2<8>, one block walks
+    # every field of its tiles, 256 workgroups over 500 / 750 tiles
+    pairs, _, tpf = DC_TILES[name]
+    p = stream_plan(lay, "block_dot2", j, NKV_X_IS_LAST if x_last else 0)
+    shape = (4, 4, 1) if name == "small" else (256, 1, lay.n_wf)
+    assert (p.pairs, p.tiles, p.grid_x, p.grid_y, p.fields_per_block, p.launches) == (pairs, tpf, *shape, 1), dict(p)
     ctx, w = make_ctx(lay, max_cols=40)
     Q = ctx.basis(j + 1)
     for i in range(j):
@@ -918,6 +945,13 @@ def test_dcgs2_coef_flags_breakdown(gpu):
 @pytest.mark.parametrize("m", [0, 1, 6, 31])
 def test_dcgs2_update_vs_numpy(gpu, name, m, with_norm):
     lay = DC_LAYOUTS[name]
+    # one launch, at most one trip per workgroup in the per-unit loop (see DC_LAYOUTS)
+    pairs, tiles, tpf = DC_TILES[name]
+    p = stream_plan(lay, "dcgs2_update", m, NKV_NORM2 if with_norm else 0)
+    loop, units = ("units", tpf + tiles - lay.n_wf * tpf) if with_norm and m < 8 else ("tiles", tiles)
+    assert (p.pairs, p.tiles, p.grid_x, p.launches, p.work_loop, p.units) == (pairs, tiles, min(tiles, 768), 1, loop,
+                                                                             units), dict(p)
+    assert loop == "tiles" or p.units <= p.grid_x
     ctx, w = make_ctx(lay, max_cols=40)
     Q = ctx.basis(m + 2)
     for i in range(m + 1):
@@ -1158,6 +1192,12 @@ def test_mgs2_step_combine_normalize_store_vs_oracle(gpu, time_dot):
     from nekstab_next_amd._lib import NKV_TIME, NKV_TIME_DOT
 
     lay = LAYOUTS["3d_scalar"]
+    # 18 small tiles: one trip per workgroup of k_axpy_dot<4>, k_block_dot<4> (j = 1), k_block_update (nkv_combine)
+    # and k_finish (their grid-stride loops: tests/test_gpu_stream_paths.py)
+    for op, j, shape in (("axpy_dot", 1, (4, 18, 18, 1)), ("block_dot", 1, (4, 4, 4, 1)),
+                         ("block_update", 7, (4, 18, 18, 1)), ("finish", 1, (4, 18, 72, 1))):
+        p = stream_plan(lay, op, j, NKV_OVERWRITE if op == "block_update" else 0)
+        assert (p.pairs, p.tiles, p.grid_x, p.launches) == shape, (op, dict(p))
     ctx, w = make_ctx(lay, max_cols=16)
     L = olayout(lay, time_in_dot=time_dot)
     d, _ = syn.diag_spectrum(lay)
