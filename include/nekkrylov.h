@@ -915,6 +915,29 @@ int nkv_orbit_stage(const nkv_layout* L, const double* minv, const double* v, in
                     const double* tr, int64_t tr_stride, const double* tacc, int64_t tacc_stride, double* tw,
                     int64_t tw_stride, double* tacc_out, int64_t tao_stride, int nfld, int zero_rest, void* stream);
 
+/* ---- coupled resolvent: the linearised convection of a complex (re/im pair) perturbation ---------------
+ * What a harmonically forced integration about a base state B needs per Horner pass (nekStab's resolvent_op,
+ * core/linear_operators.f90:309-431, with the production term of the linearised solver): B is real and does
+ * not mix the halves of a pair vector.  Conventions, arithmetic and the treatment of bad arguments and empty
+ * shards: as for the advection-diffusion entries above.
+ *
+ * nkv_linconv_crhs: replaces the two nkv_linconv_rhs calls of a pass.  L is the layout of the real fields
+ *   (n_v points per half); the halves come as separate pointers with one stride per operand (field f of the
+ *   re half at u_re + f*u_stride, of the im half at u_im + f*u_stride; likewise r_re, r_im with r_stride).  In
+ *   a pair segment the im half starts n_v doubles behind the re half: 8-byte alignment is all that is asked.
+ *     r_re = nkv_linconv_rhs(u_re; B, adjoint)        r_im = nkv_linconv_rhs(u_im; B, adjoint)        the same bits
+ *   Coordinates, geometric factors and the advecting velocity once per element group; forward: B_f staged and
+ *   differentiated once per field, its derivatives closing the production term of both halves; adjoint: one
+ *   sweep over the base fields accumulates sum_f' u_f' d_d B_f' of both halves.  23 doubles per point move at
+ *   ldim = 3, nfld = 4 where the two launches move 30 (12 against 16 at ldim = 2, nfld = 2).  LDS as
+ *   nkv_linconv_rhs (the field and flux tiles serve the re, then the im half).  nfld >= ldim; no field segment
+ *   of r_re or r_im may meet one of the other half, of u_re, u_im or of B (the halves of a pair vector
+ *   interleave, so the segments are compared, not the whole spans). */
+int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                     const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                     const double* u_re, const double* u_im, int nfld, int64_t u_stride, double* r_re, double* r_im,
+                     int64_t r_stride, int adjoint, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

@@ -177,6 +177,8 @@ _SIGNATURES = {
     "nkv_orbit_stage": (c_int, [_L, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_double, c_double, c_double,
                                 c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
                                 c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),
+    "nkv_linconv_crhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, c_int, c_int64, _P, _P,
+                                 c_int64, c_int, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

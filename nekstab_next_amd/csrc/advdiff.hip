@@ -14,7 +14,9 @@
 // classical RK4 stage of that flow (k_rk4_stage); its nonlinear right-hand side is k_advdiff_rhs with U = u.
 // Last: the periodic orbits of that flow (orbit.py) — the nonlinear and the linearised right-hand side of a
 // base state and a perturbation advanced side by side in one pass (k_burgers_tangent_rhs) and the RK4 stage
-// under a harmonic forcing that writes the orbit, with the tangent's stage in the same launch (k_orbit_stage).
+// under a harmonic forcing that writes the orbit, with the tangent's stage in the same launch (k_orbit_stage);
+// and the linearised right-hand side of the re and the im half of a pair vector in one pass (k_linconv_crhs),
+// the Horner pass of the coupled resolvent (resolvent.py).
 #include "nkv_internal.h"
 
 namespace {
@@ -723,6 +725,196 @@ __global__ __launch_bounds__(kThreads) void k_orbit_stage(int64_t n, const doubl
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The linearised convection of a complex (re/im pair) perturbation about a real base state B: B does not mix
+// the halves, so one tiled pass writes
+//   r_re = k_linconv_rhs<.., ADJ>(u_re; B)      r_im = k_linconv_rhs<.., ADJ>(u_im; B)      (the same bits)
+// where the resolvent's Horner pass would launch k_linconv_rhs twice.  Per element group the coordinates are
+// staged, the factors formed and Ub[d] read once.  Forward: B_f is staged once per field, its LDIM physical
+// derivatives wait in registers and close the production term of both halves with P_re[d], P_im[d].  Adjoint:
+// the first sweep stages and differentiates each B_f' once and accumulates P_re[d] and P_im[d] in the
+// ascending order of k_linconv_rhs.  The field tile and the three flux tiles serve the re half and then the
+// im half, as k_burgers_tangent_rhs reuses them for B and then u: the im half is staged while the re fluxes
+// are summed, and every read of the field tiles lies before the field's last barrier, so the next field is
+// staged without a barrier of its own: four barriers per field, where two launches take six.  LDS as
+// k_linconv_rhs: lx1^2 + (LDIM + 2) nt doubles.  Streams per point at LDIM = 3, nfld = 4: 3 + 4 + 8 + 8 = 23
+// doubles where two launches move 30.  Each output keeps the operand order of k_linconv_rhs.
+// NKV_CRHS_WAVES: the waves per SIMD the launch bounds ask for (0: none asked); tools/bench_coupled_resolvent.py
+// measured both and the default is the faster (CHANGELOG).
+// ------------------------------------------------------------------------------------------
+#ifndef NKV_CRHS_WAVES
+#define NKV_CRHS_WAVES 4
+#endif
+#if NKV_CRHS_WAVES > 0
+#define NKV_CRHS_BOUNDS(T) __launch_bounds__((T), NKV_CRHS_WAVES)
+#else
+#define NKV_CRHS_BOUNDS(T) __launch_bounds__((T))
+#endif
+
+template <int LDIM, int NX, bool ADJ>
+__global__ NKV_CRHS_BOUNDS((tile_threads<LDIM, NX>())) void k_linconv_crhs(
+    int64_t nel, int epb, int nfld, const double* __restrict__ Dg, const double* __restrict__ wg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ B, int64_t b_stride, const double* __restrict__ kappa, const double* __restrict__ u_re,
+    const double* __restrict__ u_im, int64_t u_stride, double* __restrict__ r_re, double* __restrict__ r_im,
+    int64_t r_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    const int nt = epb * pts;
+    double* D = lds;                         // D(i, m) at D[i*NX + m]
+    double* X = D + NX * NX;                 // coordinates, then the flux along r (of the re, then of the im half)
+    double* Y = X + nt;                      // ... along s
+    double* Z = Y + nt;                      // ... along t (3-D only)
+    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated (re, then im)
+    double* Bt = U + nt;                     // the base field being differentiated
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const PointIndex<LDIM, NX> ix(tid);
+    const double wt = ix.weight(wg);
+    const int le = tid / pts;
+    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = D + ix.j;
+    const double* Dck = D + ix.k;
+    // sum_a D_a^T of the fluxes in the three tiles
+    auto transposed_sums = [&]() {
+        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) {
+            tr = tr + Dci[m * NX] * X[q.ri + m];
+            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+        }
+        double acc = tr + ts;
+        if constexpr (LDIM == 3) {
+            double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+            acc = acc + tt;
+        }
+        return acc;
+    };
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double jacmi = 1.0 / jac;
+        const double bm = jac * wt;
+        double Ub[LDIM];       // the advecting velocity B_d
+        double Pr[LDIM];       // forward: the velocity perturbation u_re,d; adjoint: sum_f' u_re,f' d_d B_f'
+        double Pi[LDIM];       // ... of the im half
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) {
+            Ub[d] = live ? B[d * b_stride + p] : 0.0;
+            Pr[d] = (!ADJ && live) ? u_re[d * u_stride + p] : 0.0;
+            Pi[d] = (!ADJ && live) ? u_im[d * u_stride + p] : 0.0;
+        }
+        if constexpr (ADJ) {
+            for (int f = 0; f < nfld; ++f) {
+                double* T = (f & 1) ? Bt : U;   // the tile written two fields ago: a barrier lies between
+                if (live) T[tid] = B[f * b_stride + p];
+                __syncthreads();
+                if (live) {
+                    double br, bs, bt;
+                    line_sums<LDIM, NX>(q, T, br, bs, bt);
+                    const double ur = u_re[f * u_stride + p], ui = u_im[f * u_stride + p];
+#pragma unroll
+                    for (int d = 0; d < LDIM; ++d) {
+                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                        Pr[d] = f == 0 ? ur * db : Pr[d] + ur * db;
+                        Pi[d] = f == 0 ? ui * db : Pi[d] + ui * db;
+                    }
+                }
+            }
+            __syncthreads();   // every lane is done reading the last base field
+        }
+        double* tiles[3] = {X, Y, Z};
+        for (int f = 0; f < nfld; ++f) {
+            // (every lane differentiated the previous field before that field's last barrier)
+            if (live) {
+                U[tid] = u_re[f * u_stride + p];
+                if constexpr (!ADJ) Bt[tid] = B[f * b_stride + p];
+            }
+            __syncthreads();   // (and every lane has formed its factors / read the previous fluxes)
+            const double kb = live ? -kappa[f] * bm : 0.0;
+            double prod_re = 0.0, prod_im = 0.0;
+            // the fluxes F_a of the staged half into the three tiles; forward: its advection by B_vel is returned
+            auto fluxes = [&]() {
+                double ur, us, ut, adv = 0.0;
+                line_sums<LDIM, NX>(q, U, ur, us, ut);
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
+                    if constexpr (ADJ) {
+                        G[d] = kb * du - bm * Ub[d] * U[tid];
+                    } else {
+                        G[d] = kb * du;
+                        adv = adv + Ub[d] * du;
+                    }
+                }
+#pragma unroll
+                for (int a = 0; a < LDIM; ++a) {
+                    double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+                    tiles[a][tid] = F;
+                }
+                return adv;
+            };
+            double adv = 0.0;
+            if (live) {
+                if constexpr (!ADJ) {
+                    double br, bs, bt;
+                    line_sums<LDIM, NX>(q, Bt, br, bs, bt);
+#pragma unroll
+                    for (int d = 0; d < LDIM; ++d) {
+                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                        prod_re = d == 0 ? Pr[0] * db : prod_re + Pr[d] * db;
+                        prod_im = d == 0 ? Pi[0] * db : prod_im + Pi[d] * db;
+                    }
+                } else {
+#pragma unroll
+                    for (int d = 0; d < LDIM; ++d)
+                        if (f == d) {
+                            prod_re = Pr[d];
+                            prod_im = Pi[d];
+                        }
+                }
+                adv = fluxes();
+            }
+            __syncthreads();
+            if (live) {
+                const double acc = transposed_sums();
+                if constexpr (ADJ)
+                    r_re[f * r_stride + p] = f < LDIM ? acc - bm * prod_re : acc;
+                else
+                    r_re[f * r_stride + p] = (acc - bm * adv) - bm * prod_re;
+                U[tid] = u_im[f * u_stride + p];   // the re half was differentiated before the barrier above
+            }
+            __syncthreads();   // the fluxes of the re half are read, the im half is staged
+            if (live) adv = fluxes();
+            __syncthreads();
+            if (live) {
+                const double acc = transposed_sums();
+                if constexpr (ADJ)
+                    r_im[f * r_stride + p] = f < LDIM ? acc - bm * prod_im : acc;
+                else
+                    r_im[f * r_stride + p] = (acc - bm * adv) - bm * prod_im;
+            }
+        }
+    }
+}
+
 template <int LDIM, int NX>
 void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
                 const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
@@ -769,6 +961,24 @@ void launch_linconv(int64_t nel, int nfld, const double* D, const double* w, con
     else
         hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
                            epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
+}
+
+template <int LDIM, int NX>
+void launch_linconv_pair(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
+                         const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u_re,
+                         const double* u_im, int64_t u_stride, double* r_re, double* r_im, int64_t r_stride,
+                         int adjoint, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    if (adjoint)
+        hipLaunchKernelGGL((k_linconv_crhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
+                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u_re, u_im, u_stride, r_re, r_im, r_stride);
+    else
+        hipLaunchKernelGGL((k_linconv_crhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
+                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u_re, u_im, u_stride, r_re, r_im, r_stride);
 }
 
 template <int LDIM, int NX>
@@ -993,6 +1203,70 @@ int nkv_linconv_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, con
         break;
     switch (lx1) { NKV_PP_CASES(NKV_LC_RHS) }
 #undef NKV_LC_RHS
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                     const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
+                     const double* u_re, const double* u_im, int nfld, int64_t u_stride, double* r_re, double* r_im,
+                     int64_t r_stride, int adjoint, void* stream) {
+    static const char who[] = "linconv_crhs";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
+                                 nfld, ldim);
+    if (B_stride < L->n_v) return fail(NKV_EINVAL, "%s: B_stride=%lld below n_v=%lld", who, (long long)B_stride,
+                                       (long long)L->n_v);
+    if (u_stride < L->n_v) return fail(NKV_EINVAL, "%s: u_stride=%lld below n_v=%lld", who, (long long)u_stride,
+                                       (long long)L->n_v);
+    if (r_stride < L->n_v) return fail(NKV_EINVAL, "%s: r_stride=%lld below n_v=%lld", who, (long long)r_stride,
+                                       (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(B, who, "B"));
+    CHECK(need(kappa, who, "kappa"));
+    CHECK(need(u_re, who, "u_re"));
+    CHECK(need(u_im, who, "u_im"));
+    CHECK(need(r_re, who, "r_re"));
+    CHECK(need(r_im, who, "r_im"));
+    // both results are written field by field while later fields of u_re, u_im and B are still to be read.  The
+    // halves of a pair vector interleave (field f's im half lies between the re halves of f and f + 1), so
+    // where the whole spans meet the field segments decide
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        const int64_t n = L->n_v;
+        if (!(p < o + (int64_t)(nfld - 1) * os + n && o < p + (int64_t)(nfld - 1) * ps + n)) return false;
+        for (int i = 0; i < nfld; ++i)
+            for (int j = 0; j < nfld; ++j) {
+                const double *a = p + (int64_t)i * ps, *b = o + (int64_t)j * os;
+                if (a < b + n && b < a + n) return true;
+            }
+        return false;
+    };
+    if (meets(r_re, r_stride, r_im, r_stride)) return fail(NKV_EINVAL, "%s: r_re overlaps r_im", who);
+    if (meets(u_re, u_stride, r_re, r_stride) || meets(u_im, u_stride, r_re, r_stride) ||
+        meets(B, B_stride, r_re, r_stride))
+        return fail(NKV_EINVAL, "%s: r_re overlaps u_re, u_im or B", who);
+    if (meets(u_re, u_stride, r_im, r_stride) || meets(u_im, u_stride, r_im, r_stride) ||
+        meets(B, B_stride, r_im, r_stride))
+        return fail(NKV_EINVAL, "%s: r_im overlaps u_re, u_im or B", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_LC_CRHS(NX)                                                                                               \
+    case NX:                                                                                                          \
+        if (ldim == 3)                                                                                                \
+            launch_linconv_pair<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u_re, u_im, u_stride, r_re,   \
+                                       r_im, r_stride, adjoint, st);                                                  \
+        else                                                                                                          \
+            launch_linconv_pair<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u_re, u_im, u_stride, r_re,   \
+                                       r_im, r_stride, adjoint, st);                                                  \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_LC_CRHS) }
+#undef NKV_LC_CRHS
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -13,7 +13,8 @@ time ``t`` (``exponential_prop%t``).
 * :func:`resolvent_analysis` — svds of a resolvent operator on complex (re/im pair) vectors,
   sigma <- sigma**2, ``Spectrum_Sr.dat``.  The resolvent's body (forced run + inner GMRES on
   Id - Phi) is the operator's: :class:`~nekstab_next_amd.resolvent.ResolventOperator` over the model
-  propagator, or the caller's over a Nek5000 run.
+  propagator, :class:`~nekstab_next_amd.resolvent.CoupledResolventOperator` about a base state of the Burgers
+  flow, or the caller's over a Nek5000 run.
 """
 from __future__ import annotations
 
@@ -102,6 +103,8 @@ def resolvent_analysis(ctx: NekContext, R: LinearOperator, seed: NekVector, k_di
     nekStab R's body is a forced Nek5000 integration plus an inner GMRES
     (linear_operators.f90:348-431) — any operator with that interface plugs in:
     :class:`~nekstab_next_amd.resolvent.ResolventOperator` is that body over the model propagator,
+    :class:`~nekstab_next_amd.resolvent.CoupledResolventOperator` the same about a base state (the
+    linearised convection with its production term),
     :class:`~nekstab_next_amd.operators.ComplexDiagOperator` the synthetic, exactly known one.
     The reference seeds re and im separately (prepare_seed on U%re, U%im, :147-148); here the
     seed pair is normalised as one vector (the bidiagonalisation only needs its direction).  The

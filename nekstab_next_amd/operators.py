@@ -233,7 +233,8 @@ class ComplexDiagOperator(LinearOperator):
     the cmplx dot re.re + im.im.  ``cr``/``ci`` are padded pair-layout vectors read at the re rows
     (:func:`~nekstab_next_amd.synthetic.resolvent_diag`).  The synthetic, exactly known counterpart of
     nekStab's ``resolvent_op`` (core/linear_operators.f90:309-431); its body as a time stepper on the GLL mesh
-    (forced integration + inner GMRES on ``I - Phi``) is :class:`~nekstab_next_amd.resolvent.ResolventOperator`."""
+    (forced integration + inner GMRES on ``I - Phi``) is :class:`~nekstab_next_amd.resolvent.ResolventOperator`,
+    about a base state :class:`~nekstab_next_amd.resolvent.CoupledResolventOperator`."""
 
     def __init__(self, ctx: NekContext, cr, ci):
         from .layout import PairLayout

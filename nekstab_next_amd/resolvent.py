@@ -25,13 +25,17 @@ the same algorithm on ``L†`` with ``-omega`` (``G† = L† + i omega``): the 
 product weighted by ``adv.bm1`` up to the inner tolerance, not up to a time-discretisation error.  The
 deviations from the reference's real-state form are DESIGN §3's.
 
+:class:`CoupledResolventOperator` is the same algorithm about a base state ``B``: ``L = L_B`` of
+:class:`~nekstab_next_amd.burgers.LinearisedConvection`, production term ``(u'·∇)B`` included, the non-normal
+part that makes resolvent gains large.
+
 Stability: every ``dt · (lambda - i omega)``, lambda in the spectrum of L, inside RK4's region, roughly
 ``dt · rho(L - i omega) <~ 2.78``.  On the edge of that region phi vanishes (z = -2.785 and
 z = -0.607 ± 2.872i), where ``I - Phi`` loses the forcing's component: keep ``dt`` inside.
 
-Each Horner pass is ``nkv_advdiff_rhs`` on the re and on the im halves, one ``dsavg`` batch of the
-``2 · n_wf`` segments and one fused complex stage (``nkv_advdiff_cstage``, include/nekkrylov.h).  The work
-vectors are allocated once and nothing synchronises with the host outside GMRES.
+Each Horner pass is ``nkv_advdiff_rhs`` on the re and on the im halves (coupled: one ``nkv_linconv_crhs`` for
+both), one ``dsavg`` batch of the ``2 · n_wf`` segments and one fused complex stage (``nkv_advdiff_cstage``,
+include/nekkrylov.h).  The work vectors are allocated once and nothing synchronises with the host outside GMRES.
 """
 from __future__ import annotations
 
@@ -78,12 +82,7 @@ class ResolventOperator(LinearOperator):
 
     def __init__(self, pctx: NekContext, adv: AdvectionDiffusion, omega: float, tol: float = 1e-10, kdim: int = 60,
                  maxiter: int = 20):
-        from .burgers import LinearisedConvection
-
-        if isinstance(adv, LinearisedConvection):
-            raise ValueError("ResolventOperator: a LinearisedConvection is refused: the resolvent steps with "
-                             "nkv_advdiff_rhs and would silently drop the production term (u'.grad)B; a coupled "
-                             "resolvent is not implemented (DESIGN §10)")
+        self._check_model(adv)
         base = adv.ctx.layout
         if not isinstance(pctx.layout, PairLayout) or pctx.layout != pair_layout(base):
             raise ValueError("ResolventOperator: pctx must be a context on pair_layout(adv.ctx.layout)")
@@ -123,6 +122,17 @@ class ResolventOperator(LinearOperator):
         self._avg_ptrs = [h + 8 * k * psv for k in range(nf) for h in self._halves(rp)]
 
     # ---- plumbing ----
+    @staticmethod
+    def _check_model(adv) -> None:
+        """The models this class steps: anything but a LinearisedConvection, whose production term
+        ``nkv_advdiff_rhs`` does not have."""
+        from .burgers import LinearisedConvection
+
+        if isinstance(adv, LinearisedConvection):
+            raise ValueError("ResolventOperator: a LinearisedConvection is refused: the resolvent steps with "
+                             "nkv_advdiff_rhs and would silently drop the production term (u'.grad)B; "
+                             "CoupledResolventOperator is the resolvent about a base state")
+
     def _halves(self, ptr: int):
         return ptr, ptr + self._half
 
@@ -189,7 +199,7 @@ class ResolventOperator(LinearOperator):
                            maxiter=self.maxiter)
         self.last_gmres = dict(info=info, residuals=hist, adjoint=adjoint)
         if info != 0:
-            raise RuntimeError(f"ResolventOperator: the inner GMRES did not converge (omega={self.omega}, kdim={self.kdim}, "
+            raise RuntimeError(f"{type(self).__name__}: the inner GMRES did not converge (omega={self.omega}, kdim={self.kdim}, "
                                f"maxiter={self.maxiter}, tol={self.tol}): residuals {hist}")
 
     def matvec(self, x: NekVector, y: NekVector) -> None:
@@ -199,4 +209,42 @@ class ResolventOperator(LinearOperator):
         self._apply(x, y, True)
 
 
-__all__ = ["ResolventOperator", "pair_context"]
+class CoupledResolventOperator(ResolventOperator):
+    """``y = (i omega - L_B)^-1 Pi x`` on complex pair vectors and, as ``rmatvec``, ``(-i omega - L_B†)^-1 Pi x``:
+    the resolvent about a base state ``B``, with ``L_B`` the linearised convection of
+    :class:`~nekstab_next_amd.burgers.LinearisedConvection` (advection by ``B``'s velocity, diffusion and the
+    production term ``(u'·∇)B``) and ``L_B†`` its exact discrete adjoint.
+
+    Everything is :class:`ResolventOperator`'s (``project``, ``forced_run``, ``propagate``, the inner GMRES on
+    ``I - Phi``, ``last_gmres``, the context checks, the zeroing of pressure and time) except the local
+    right-hand side: ``B`` is real and does not mix the halves, so one ``nkv_linconv_crhs`` per Horner pass
+    writes both (the bits of ``nkv_linconv_rhs`` on each half), followed by the same ``dsavg`` batch.
+    ``pair_context(lin)`` builds ``pctx``.  ``lin.B`` is bound at construction: ``lin.set_base(q)`` afterwards
+    writes into it in place and takes effect on the next product without rebuilding the operator.  Anything
+    that is not a ``LinearisedConvection`` is refused."""
+
+    def __init__(self, pctx: NekContext, lin, omega: float, tol: float = 1e-10, kdim: int = 60, maxiter: int = 20):
+        super().__init__(pctx, lin, omega, tol=tol, kdim=kdim, maxiter=maxiter)
+        base = lin.ctx.layout
+        self.lin = lin
+        self._bound = self._bound + (lin.B,)
+        self._crhs_head = (base.lx1, base.ldim, lin.D.data_ptr(), lin.w.data_ptr(), *lin._xyz_ptrs(), lin.B.data_ptr(),
+                           base.sv, lin.kappa.data_ptr())
+
+    @staticmethod
+    def _check_model(adv) -> None:
+        from .burgers import LinearisedConvection
+
+        if not isinstance(adv, LinearisedConvection):
+            raise ValueError(f"CoupledResolventOperator: needs a LinearisedConvection (the base state and its production "
+                             f"term), not a {type(adv).__name__}; ResolventOperator steps a plain AdvectionDiffusion")
+
+    def _local_rhs(self, src: int, adjoint: bool, st: int) -> None:
+        """r <- dsavg of the linearised local right-hand sides of both halves of the n_wf fields at ``src``."""
+        psv, rp = self.ctx.layout.sv, self._r.data_ptr()
+        self.adv.ctx.call("nkv_linconv_crhs", *self._crhs_head, *self._halves(src), self.ctx.layout.n_wf, psv,
+                          *self._halves(rp), psv, int(adjoint), st)
+        average_segments(self.adv.face_average, self._avg_ptrs)
+
+
+__all__ = ["CoupledResolventOperator", "ResolventOperator", "pair_context"]
