@@ -893,6 +893,16 @@ int nkv_rk4_stage(const nkv_layout* L, const double* v, int64_t v_stride, const 
  *   self-advection, the diffusion flux of B and the production term.  19 doubles per point move at ldim = 3,
  *   nfld = 4 where the two launches move 29.  LDS as nkv_linconv_rhs (the flux tiles serve B, then u).
  *   nfld >= ldim; the spans of r_B and r_u must not meet each other, u or B.
+ * nkv_burgers_backward_rhs: the right-hand side of the backward sweep of a checkpointed adjoint, in which the
+ *   adjoint runs backwards through one segment of the orbit while the segment before it is recomputed from
+ *   its checkpoint.  For the base state X being advanced, a stored stage state S and the adjoint variable u
+ *   of nfld fields each, one tiled pass writes both LOCAL right-hand sides
+ *     r_X,f = r_advdiff,f(X; U = X_vel)               the bits of forward nkv_advdiff_rhs with u = U = X
+ *     r_u,f = adjoint nkv_linconv_rhs(u; S)_f         the same bits
+ *   Coordinates and geometric factors once per element group; the X sweep first, then the sweep over the
+ *   fields of S that closes sum_f' u_f' d_d S_f', then the sweep over u.  23 doubles per point move at
+ *   ldim = 3, nfld = 4 where the two launches move 29.  LDS as nkv_linconv_rhs.  nfld >= ldim; the spans of
+ *   r_X and r_u must not meet each other, X, S or u; X and S are only read and may be one state.
  * nkv_orbit_stage: one RK4 stage of the base flow under the harmonic forcing g(t) = g0 + cos(wt) gc +
  *   sin(wt) gs (nekStab forces through userf; here the three parts are fields and c, s the cos and sin of the
  *   stage's phase, formed by the host) and, when tr is not NULL, of the tangent in the same launch.  Base half,
@@ -908,6 +918,10 @@ int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double
                             const double* ym, const double* zm, const double* B, int64_t B_stride, const double* kappa,
                             const double* u, int nfld, int64_t u_stride, double* r_B, int64_t rB_stride, double* r_u,
                             int64_t ru_stride, void* stream);
+int nkv_burgers_backward_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                             const double* ym, const double* zm, const double* X, int64_t X_stride, const double* S,
+                             int64_t S_stride, const double* kappa, const double* u, int nfld, int64_t u_stride,
+                             double* r_X, int64_t rX_stride, double* r_u, int64_t ru_stride, void* stream);
 int nkv_orbit_stage(const nkv_layout* L, const double* minv, const double* v, int64_t v_stride, const double* r,
                     int64_t r_stride, const double* g0, const double* gc, const double* gs, int64_t g_stride, double c,
                     double s, double a, double b, int first, const double* acc, int64_t acc_stride, double* w,

@@ -32,6 +32,6 @@ def __getattr__(name):
         return getattr(importlib.import_module(".resolvent", __name__), name)
     if name in ("LinearisedConvection", "ViscousBurgers"):   # the nonlinear flow and its linearisation (burgers.py)
         return getattr(importlib.import_module(".burgers", __name__), name)
-    if name in ("OrbitFlow", "OrbitPropagator"):   # the time-periodic base flow and its tangent (orbit.py)
+    if name in ("OrbitFlow", "OrbitPropagator", "checkpoint_schedule"):   # the time-periodic base flow and its tangent (orbit.py)
         return getattr(importlib.import_module(".orbit", __name__), name)
     raise AttributeError(name)

@@ -174,6 +174,8 @@ _SIGNATURES = {
                               _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     "nkv_burgers_tangent_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int64, _P,
                                         c_int64, _P, c_int64, _P]),
+    "nkv_burgers_backward_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int,
+                                         c_int64, _P, c_int64, _P, c_int64, _P]),
     "nkv_orbit_stage": (c_int, [_L, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_double, c_double, c_double,
                                 c_double, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
                                 c_int64, _P, c_int64, _P, c_int64, c_int, c_int, _P]),

@@ -16,7 +16,9 @@
 // base state and a perturbation advanced side by side in one pass (k_burgers_tangent_rhs) and the RK4 stage
 // under a harmonic forcing that writes the orbit, with the tangent's stage in the same launch (k_orbit_stage);
 // and the linearised right-hand side of the re and the im half of a pair vector in one pass (k_linconv_crhs),
-// the Horner pass of the coupled resolvent (resolvent.py).
+// the Horner pass of the coupled resolvent (resolvent.py); and the backward sweep of a checkpointed adjoint,
+// the nonlinear right-hand side of a segment being recomputed and the adjoint one about a stored stage state in
+// one pass (k_burgers_backward_rhs).
 #include "nkv_internal.h"
 
 namespace {
@@ -915,6 +917,181 @@ __global__ NKV_CRHS_BOUNDS((tile_threads<LDIM, NX>())) void k_linconv_crhs(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The backward sweep of a checkpointed adjoint (orbit.py): while the adjoint runs backwards through one segment
+// of the orbit, the segment before it is recomputed forwards.  For the base state X being advanced, a stored
+// stage state S and the adjoint variable u of nfld fields each, one tiled pass writes both local right-hand
+// sides
+//   rX_f = r_advdiff,f(X; U = X_vel)                                   (the bits of k_advdiff_rhs<.., false>)
+//   ru_f = r_advdiff,adj,f(u; U = S_vel) - [f < LDIM] bm1 sum_f' u_f' d_f S_f'   (k_linconv_rhs<.., true>)
+// The coordinates are staged and the factors formed once per group.  First the X sweep (field tile and LDIM
+// flux tiles), then the adjoint: the sweep over the fields of S that accumulates sum_f' u_f' d_d S_f' in LDIM
+// registers, then the sweep over u through the same flux tiles.  Every staged field alternates between the
+// two field tiles (U, Bt) through all three sweeps, so a field is staged while lanes may still differentiate
+// the one before it and a tile is rewritten only with a barrier behind its last reader: two barriers per
+// field in the X sweep and in the sweep over u, one in the sweep over S, 2 + 5 nfld per group where the two
+// kernels take 4 + 7 nfld.  LDS as k_linconv_rhs: lx1^2 + (LDIM + 2) nt doubles, sized at the launch, below
+// 64 KiB (no attribute to raise).  Each output keeps the operand order of the kernel it restates.  Streams per
+// point at LDIM = 3, nfld = 4: 3 + 4 + 4 + 4 + 8 = 23 doubles where the two launches move 14 + 15 = 29.
+// NKV_BWD_WAVES: the waves per SIMD the launch bounds ask for (0: none asked).  At lx1 = 8 in 3-D the kernel
+// takes 126 VGPRs at four waves either way (the same code); at odd lx1 in 3-D the request costs two or three
+// spilled registers where 130-132 VGPRs would leave three waves, the trade k_burgers_tangent_rhs measured.
+// ------------------------------------------------------------------------------------------
+#ifndef NKV_BWD_WAVES
+#define NKV_BWD_WAVES 4
+#endif
+#if NKV_BWD_WAVES > 0
+#define NKV_BWD_BOUNDS(T) __launch_bounds__((T), NKV_BWD_WAVES)
+#else
+#define NKV_BWD_BOUNDS(T) __launch_bounds__((T))
+#endif
+
+template <int LDIM, int NX>
+__global__ NKV_BWD_BOUNDS((tile_threads<LDIM, NX>())) void k_burgers_backward_rhs(
+    int64_t nel, int epb, int nfld, const double* __restrict__ Dg, const double* __restrict__ wg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ Xs, int64_t x_stride, const double* __restrict__ Sb, int64_t s_stride,
+    const double* __restrict__ kappa, const double* __restrict__ u, int64_t u_stride, double* __restrict__ rX,
+    int64_t rx_stride, double* __restrict__ ru, int64_t ru_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    const int nt = epb * pts;
+    double* D = lds;                         // D(i, m) at D[i*NX + m]
+    double* X = D + NX * NX;                 // coordinates, then the flux along r (of X, then of u)
+    double* Y = X + nt;                      // ... along s
+    double* Z = Y + nt;                      // ... along t (3-D only)
+    double* U = LDIM == 3 ? Z + nt : Z;      // the two field tiles: staged fields alternate between them
+    double* Bt = U + nt;
+    const int tid = threadIdx.x;
+    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+    const TilePoint<LDIM, NX> q(D, tid, nt);
+    const PointIndex<LDIM, NX> ix(tid);
+    const double wt = ix.weight(wg);
+    const int le = tid / pts;
+    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = D + ix.j;
+    const double* Dck = D + ix.k;
+    // sum_a D_a^T of the fluxes in the three tiles
+    auto transposed_sums = [&]() {
+        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) {
+            tr = tr + Dci[m * NX] * X[q.ri + m];
+            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+        }
+        double acc = tr + ts;
+        if constexpr (LDIM == 3) {
+            double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+            acc = acc + tt;
+        }
+        return acc;
+    };
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double jacmi = 1.0 / jac;
+        const double bm = jac * wt;
+        double* tiles[3] = {X, Y, Z};
+        // G_d -> the fluxes F_a into the three tiles
+        auto write_fluxes = [&](const double (&G)[LDIM]) {
+#pragma unroll
+            for (int a = 0; a < LDIM; ++a) {
+                double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+                for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+                tiles[a][tid] = F;
+            }
+        };
+        int stage = 0;         // fields staged so far in this group: the next one goes to tile (stage & 1)
+        double Ub[LDIM];       // the advecting velocity: X_d, then S_d
+        // ---- the X sweep: k_advdiff_rhs<.., false> with u = U = X ----
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) Ub[d] = live ? Xs[d * x_stride + p] : 0.0;
+        for (int f = 0; f < nfld; ++f, ++stage) {
+            double* T = (stage & 1) ? Bt : U;   // last read two fields ago: a barrier lies between
+            if (live) T[tid] = Xs[f * x_stride + p];
+            __syncthreads();   // (every lane has formed its factors / read the previous field's fluxes)
+            double adv = 0.0;
+            if (live) {
+                double ur, us, ut;
+                line_sums<LDIM, NX>(q, T, ur, us, ut);
+                const double kb = -kappa[f] * bm;
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
+                    G[d] = kb * du;
+                    adv = adv + Ub[d] * du;
+                }
+                write_fluxes(G);
+            }
+            __syncthreads();
+            if (live) rX[f * rx_stride + p] = transposed_sums() - bm * adv;
+        }
+        // ---- the adjoint: k_linconv_rhs<.., true> of u about S ----
+        double P[LDIM];        // sum_f' u_f' d_d S_f'
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) {
+            Ub[d] = live ? Sb[d * s_stride + p] : 0.0;
+            P[d] = 0.0;
+        }
+        for (int f = 0; f < nfld; ++f, ++stage) {
+            double* T = (stage & 1) ? Bt : U;
+            if (live) T[tid] = Sb[f * s_stride + p];
+            __syncthreads();
+            if (live) {
+                double br, bs, bt;
+                line_sums<LDIM, NX>(q, T, br, bs, bt);
+                const double uf = u[f * u_stride + p];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                    P[d] = f == 0 ? uf * db : P[d] + uf * db;
+                }
+            }
+        }
+        for (int f = 0; f < nfld; ++f, ++stage) {
+            double* T = (stage & 1) ? Bt : U;
+            if (live) T[tid] = u[f * u_stride + p];
+            __syncthreads();   // (every lane has read the fluxes of the field before: of X the first time)
+            double prod = 0.0;
+            if (live) {
+                double ur, us, ut;
+                line_sums<LDIM, NX>(q, T, ur, us, ut);
+                const double kb = -kappa[f] * bm;
+                double G[LDIM];
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
+                    G[d] = kb * du - bm * Ub[d] * T[tid];
+                }
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d)
+                    if (f == d) prod = P[d];
+                write_fluxes(G);
+            }
+            __syncthreads();
+            if (live) {
+                const double acc = transposed_sums();
+                ru[f * ru_stride + p] = f < LDIM ? acc - bm * prod : acc;
+            }
+        }
+    }
+}
+
 template <int LDIM, int NX>
 void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
                 const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
@@ -992,6 +1169,21 @@ void launch_tangent(int64_t nel, int nfld, const double* D, const double* w, con
     const int grid = (int)std::min<int64_t>(groups, 16384);
     hipLaunchKernelGGL((k_burgers_tangent_rhs<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
                        nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, rB, rb_stride, ru, ru_stride);
+}
+
+template <int LDIM, int NX>
+void launch_backward(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
+                     const double* zm, const double* X, int64_t x_stride, const double* Sb, int64_t s_stride,
+                     const double* kappa, const double* u, int64_t u_stride, double* rX, int64_t rx_stride, double* ru,
+                     int64_t ru_stride, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 16384);
+    hipLaunchKernelGGL((k_burgers_backward_rhs<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
+                       nfld, D, w, xm, ym, zm, X, x_stride, Sb, s_stride, kappa, u, u_stride, rX, rx_stride, ru,
+                       ru_stride);
 }
 
 }  // namespace
@@ -1376,6 +1568,61 @@ int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double
         break;
     switch (lx1) { NKV_PP_CASES(NKV_BT_RHS) }
 #undef NKV_BT_RHS
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_burgers_backward_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
+                             const double* ym, const double* zm, const double* X, int64_t X_stride, const double* Sb,
+                             int64_t S_stride, const double* kappa, const double* u, int nfld, int64_t u_stride,
+                             double* r_X, int64_t rX_stride, double* r_u, int64_t ru_stride, void* stream) {
+    static const char who[] = "burgers_backward_rhs";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the first ldim fields of X and S advect)", who,
+                                 nfld, ldim);
+    if (X_stride < L->n_v || S_stride < L->n_v || u_stride < L->n_v || rX_stride < L->n_v || ru_stride < L->n_v)
+        return fail(NKV_EINVAL,
+                    "%s: strides X_stride=%lld S_stride=%lld u_stride=%lld rX_stride=%lld ru_stride=%lld below n_v=%lld",
+                    who, (long long)X_stride, (long long)S_stride, (long long)u_stride, (long long)rX_stride,
+                    (long long)ru_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(X, who, "X"));
+    CHECK(need(Sb, who, "S"));
+    CHECK(need(kappa, who, "kappa"));
+    CHECK(need(u, who, "u"));
+    CHECK(need(r_X, who, "r_X"));
+    CHECK(need(r_u, who, "r_u"));
+    // both results are written field by field while later fields of X, S and u are still to be read; X and S
+    // are only read and may be one state
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        const double* pe = p + (int64_t)(nfld - 1) * ps + L->n_v;
+        const double* oe = o + (int64_t)(nfld - 1) * os + L->n_v;
+        return p < oe && o < pe;
+    };
+    if (meets(r_X, rX_stride, r_u, ru_stride)) return fail(NKV_EINVAL, "%s: r_X overlaps r_u", who);
+    if (meets(X, X_stride, r_X, rX_stride) || meets(Sb, S_stride, r_X, rX_stride) || meets(u, u_stride, r_X, rX_stride))
+        return fail(NKV_EINVAL, "%s: r_X overlaps X, S or u", who);
+    if (meets(X, X_stride, r_u, ru_stride) || meets(Sb, S_stride, r_u, ru_stride) || meets(u, u_stride, r_u, ru_stride))
+        return fail(NKV_EINVAL, "%s: r_u overlaps X, S or u", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_BB_RHS(NX)                                                                                               \
+    case NX:                                                                                                         \
+        if (ldim == 3)                                                                                               \
+            launch_backward<3, NX>(nel, nfld, D, w, xm, ym, zm, X, X_stride, Sb, S_stride, kappa, u, u_stride, r_X,   \
+                                   rX_stride, r_u, ru_stride, st);                                                   \
+        else                                                                                                         \
+            launch_backward<2, NX>(nel, nfld, D, w, xm, ym, zm, X, X_stride, Sb, S_stride, kappa, u, u_stride, r_X,   \
+                                   rX_stride, r_u, ru_stride, st);                                                   \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_BB_RHS) }
+#undef NKV_BB_RHS
     NKV_LAUNCHED();
     return NKV_OK;
 }

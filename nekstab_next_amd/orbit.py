@@ -33,9 +33,18 @@ The chain, as nekStab runs it (forced UPO by Newton, then Floquet multipliers, a
     op = of.linearized(q)
     krylov_schur(ctx, LegacyMatvec(3.11, op), seed, cfg)      # 3.21: adjoint, 3.31: intracycle growth
 
+Checkpointed storage (``OrbitFlow(…, checkpoint=c)``).  The stored orbit takes ``4·nsteps`` stage states; with
+``checkpoint=c`` the period is cut into ``J = ceil(nsteps/c)`` segments of ``c`` steps (the last may be shorter)
+and only the start state of every segment is kept, next to two windows of the stage states of one segment each.
+``rmatvec`` then walks the segments backwards: it re-runs the base flow over a segment from its checkpoint into
+a window (the same launches on the same inputs as ``propagate``, so the same bits) and runs the adjoint steps
+about that window.  :func:`checkpoint_schedule` is that walk as a list of operations.  Pipelined (``fused=True``)
+the adjoint of segment ``j`` and the recomputation of segment ``j − 1`` advance in the same launches: per stage
+one ``nkv_burgers_backward_rhs``, one ``dsavg`` batch of the ``2·n_wf`` segments and one ``nkv_orbit_stage`` with
+both halves.  Stored, sequential and pipelined ``rmatvec`` give the same bits.
+
 Out of scope: the natural UPO Newton loop of 2.1, whose period — and with it ``dt`` — changes per
-iterate (``time_derivative`` feeds its period row; the pressure-free flow has no known autonomous cycle), and
-checkpointed adjoints (``rmatvec`` needs the whole orbit stored).
+iterate (``time_derivative`` feeds its period row; the pressure-free flow has no known autonomous cycle).
 """
 from __future__ import annotations
 
@@ -51,6 +60,49 @@ from .vector import NekVector
 THETA = (0.0, 0.5, 0.5, 1.0)
 
 
+def auto_checkpoint(nsteps: int) -> int:
+    """``checkpoint="auto"``: ``max(1, round(sqrt(nsteps/8)))``, the minimiser of the ``nsteps/c + 8c`` slots of
+    checkpoints and windows."""
+    return max(1, round(math.sqrt(nsteps / 8)))
+
+
+def _segment_length(nsteps: int, c) -> int:
+    if c == "auto":
+        return auto_checkpoint(nsteps)
+    if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+        raise ValueError(f'checkpoint={c!r}: the steps per segment, an int >= 1, or "auto"')
+    return c
+
+
+def checkpoint_schedule(nsteps: int, c, fused: bool = True) -> list:
+    """The backward walk of a checkpointed ``rmatvec`` over ``J = ceil(nsteps/c)`` segments (segment ``j``: steps
+    ``[j·c, min((j+1)·c, nsteps))``; its window is ``j & 1``), as a list of
+
+        ("recompute", j, window)    re-run the base over segment j from checkpoint j into the window
+        ("adjoint", j, window)      the adjoint steps end−1 … start of segment j about the window
+        ("pair", ja, jr, k)         adjoint step end−1−t of segment ja (window ja & 1) with recompute step
+                                    start+t of segment jr = ja − 1 (window jr & 1) for t < k; k is all of ja,
+                                    and the steps of jr past k (only a last segment is shorter) follow unfused
+
+    ``fused=False``: recompute then adjoint, segment by segment.  ``fused=True``: the last segment is recomputed
+    alone, every other recomputation rides with the adjoint of the segment after it, and the adjoint of segment 0
+    runs alone.  Pure: no device, no state."""
+    if isinstance(nsteps, bool) or not isinstance(nsteps, int) or nsteps < 1:
+        raise ValueError(f"nsteps={nsteps!r} must be an int >= 1")
+    c = _segment_length(nsteps, c)
+    J = -(-nsteps // c)
+    ops = [("recompute", J - 1, (J - 1) & 1)]
+    if fused:
+        ops += [("pair", j, j - 1, min((j + 1) * c, nsteps) - j * c) for j in range(J - 1, 0, -1)]
+        ops.append(("adjoint", 0, 0))
+    else:
+        for j in range(J - 1, -1, -1):
+            if j < J - 1:
+                ops.append(("recompute", j, j & 1))
+            ops.append(("adjoint", j, j & 1))
+    return ops
+
+
 class OrbitFlow:
     """``Φ_T`` of a :class:`ViscousBurgers` under ``g(t) = g0 + cos(ωt)·cos + sin(ωt)·sin`` (module docstring);
     ``g0`` is the flow's own constant forcing.  ``cos`` / ``sin``: None, a :class:`NekVector` or ``n_wf`` arrays
@@ -61,30 +113,58 @@ class OrbitFlow:
     rank); ``store=False`` keeps none and the propagator advances the base next to the perturbation.
     ``residual`` and ``linearized`` are the two callables of ``newton.newton_krylov``; with ``cos = sin = None``
     ``propagate`` equals ``ViscousBurgers.propagate`` bit for bit.  The flow itself is left as it is, except
-    that its work vectors are used."""
+    that its work vectors are used.
 
-    def __init__(self, flow: ViscousBurgers, cos=None, sin=None, store: bool = True):
+    ``checkpoint=c`` (an int >= 1, or ``"auto"`` for ``max(1, round(sqrt(nsteps/8)))``; only with ``store=True``)
+    keeps, instead of the whole orbit, the start state of each of the ``J = ceil(nsteps/c)`` segments of ``c``
+    steps, two windows of the ``4·min(c, nsteps)`` stage states of one segment each and the four slots of the
+    side-by-side ``matvec``: ``(J + 8·min(c, nsteps) + 4)·n_wf·sv·8`` bytes (``self.orbit_bytes``), about
+    ``5.7·sqrt(nsteps)`` stage states with ``"auto"``.  ``propagate`` fills the windows in turn and writes the end
+    of a segment straight into the next checkpoint; each window remembers which segment of which run it holds,
+    and a segment it still holds is not recomputed.  ``matvec`` advances the base next to the perturbation, as
+    with ``store=False``; ``rmatvec`` recomputes segment by segment (module docstring).  When a segment is
+    recomputed the end state of its last step, which the next checkpoint already holds, goes to the first of the
+    ``matvec`` slots as scratch: no checkpoint is written twice.  Every result carries the bits of the stored
+    mode."""
+
+    def __init__(self, flow: ViscousBurgers, cos=None, sin=None, store: bool = True, checkpoint=None):
         ctx, lay = flow.ctx, flow.ctx.layout
         self.flow, self.lin, self.ctx, self.store = flow, flow.lin, ctx, bool(store)
         self.dt, self.nsteps, self.tau = flow.dt, flow.nsteps, flow.tau
         self.bm1, self.mask, self.minv = flow.bm1, flow.mask, flow.minv
+        if checkpoint is not None and not self.store:
+            raise ValueError("checkpoint= cuts a stored orbit into segments: it needs store=True")
+        self.checkpoint = None if checkpoint is None else _segment_length(self.nsteps, checkpoint)
         f64 = dict(dtype=torch.float64, device=ctx.device)
         self._seg = lay.n_wf * lay.sv                       # doubles of one stage state
-        slots = 4 * self.nsteps if self.store else 4
+        if self.checkpoint:
+            c = self.checkpoint
+            self._nseg = -(-self.nsteps // c)               # J
+            self._wlen = min(c, self.nsteps)                # steps per window
+            slots = self._nseg + 8 * self._wlen + 4         # checkpoints | window 0 | window 1 | matvec's slots
+        else:
+            slots = 4 * self.nsteps if self.store else 4
         self.orbit_bytes = 8 * slots * self._seg
         try:
             self._orbit = torch.empty(slots * self._seg + 2, **f64)
         except RuntimeError as e:   # (torch.OutOfMemoryError is one)
-            raise MemoryError(f"the orbit buffer needs 4·nsteps·n_wf·sv·8 = {self.orbit_bytes} bytes on the device "
-                              f"(nsteps={self.nsteps}, n_wf={lay.n_wf}, sv={lay.sv}); store=False keeps no orbit") from e
+            what = (f"{slots}·n_wf·sv·8 (checkpoint={self.checkpoint})" if self.checkpoint else "4·nsteps·n_wf·sv·8")
+            raise MemoryError(f"the orbit buffer needs {what} = {self.orbit_bytes} bytes on the device "
+                              f"(nsteps={self.nsteps}, n_wf={lay.n_wf}, sv={lay.sv}); checkpoint= keeps the start of "
+                              f"every segment and recomputes the rest, store=False keeps no orbit") from e
         self._gc = self._part(cos)
         self._gs = self._part(sin)
         self._q0 = torch.zeros(self._seg + 2, **f64)        # the weighted rows the orbit started from
         self._tacc = torch.zeros(self._seg + 2, **f64)      # the tangent's accumulator
-        self._r2 = None if self.store else torch.zeros(2 * self._seg + 2, **f64)   # r_B | r_u of the fused pass
+        side = self.checkpoint or not self.store            # the base advances next to a perturbation
+        self._r2 = torch.zeros(2 * self._seg + 2, **f64) if side else None   # r_B | r_u of the fused passes
         self._out = ctx.vector() if self.store else None    # where linearized() lets a re-run end
         self._td = None                                     # the stage states of time_derivative, on first use
         self._valid = False
+        self._run = 0                                       # counts propagate: with a segment, a window's tag
+        self._wtag = [None, None]                           # (run, segment) each window holds
+        self._plan = {f: checkpoint_schedule(self.nsteps, self.checkpoint, fused=f)
+                      for f in (False, True)} if self.checkpoint else None
         self.prop = OrbitPropagator(self)
 
     # ---- plumbing ----
@@ -97,8 +177,41 @@ class OrbitFlow:
         return torch.cat([flow._tmp.storage[:n], flow._tmp.storage.new_zeros(2)])
 
     def _slot(self, n: int, i: int) -> int:
-        """The address of stage state i of step n (one step's four slots when nothing is stored)."""
-        return self._orbit.data_ptr() + 8 * ((4 * n if self.store else 0) + i) * self._seg
+        """The address of stage state i of step n (one step's four slots when nothing is stored).  Checkpointed:
+        in the window of the step's segment, but the first state of a segment is its checkpoint."""
+        if self.checkpoint:
+            j, k = divmod(n, self.checkpoint)
+            at = j if k == 0 and i == 0 else self._nseg + 4 * self._wlen * (j & 1) + 4 * k + i
+        else:
+            at = (4 * n if self.store else 0) + i
+        return self._orbit.data_ptr() + 8 * at * self._seg
+
+    def _side_slot(self, i: int) -> int:
+        """Stage state i of the step the side-by-side ``matvec`` is at."""
+        at = self._nseg + 8 * self._wlen + i if self.checkpoint else i
+        return self._orbit.data_ptr() + 8 * at * self._seg
+
+    def _span(self, j: int):
+        """The steps [start, end) of segment j."""
+        return j * self.checkpoint, min((j + 1) * self.checkpoint, self.nsteps)
+
+    def _holds(self, j: int) -> bool:
+        return self._wtag[j & 1] == (self._run, j)
+
+    def _recompute(self, j: int, k0: int = 0) -> None:
+        """Steps k0 … of segment j again from its checkpoint (or from step k0's first state) into the segment's
+        window: the launches of ``propagate``; the end of the last step goes to scratch."""
+        if k0 == 0 and self._holds(j):
+            return
+        start, end = self._span(j)
+        self._wtag[j & 1] = None
+        for n in range(start + k0, end):
+            self._base_step(n, [self._slot(n, i) for i in range(4)], self._next(n), 0)
+        self._wtag[j & 1] = (self._run, j)
+
+    def _next(self, n: int) -> int:
+        """Where a recomputed step n ends: the first state of step n + 1 in the window, or scratch."""
+        return self._side_slot(0) if (n + 1) % self.checkpoint == 0 or n + 1 == self.nsteps else self._slot(n + 1, 0)
 
     def phase(self, n: int, theta: float):
         ph = 2.0 * math.pi * (n + theta) / self.nsteps
@@ -141,10 +254,15 @@ class OrbitFlow:
         the stage states of this run."""
         N = self.nsteps
         self._q0[: self._seg].copy_(q.storage[: self._seg])
+        self._run += 1
+        self._wtag = [None, None]
         self._project(q.ptr, self._slot(0, 0))
         for n in range(N):
             last = n == N - 1
             self._base_step(n, [self._slot(n, i) for i in range(4)], out.ptr if last else self._slot(n + 1, 0), int(last))
+            if self.checkpoint and (last or (n + 1) % self.checkpoint == 0):
+                j = n // self.checkpoint
+                self._wtag[j & 1] = (self._run, j)
         self._valid = True
 
     def residual(self, q: NekVector, f: NekVector) -> None:
@@ -189,7 +307,14 @@ class OrbitPropagator(LinearOperator):
     one ``dsavg`` batch and ``nkv_rk4_stage``.  With ``store=False`` (the reference's ``ifbase = .true.``)
     ``matvec`` advances the base from the state ``linearized`` was given next to the perturbation: one
     ``nkv_burgers_tangent_rhs``, one ``dsavg`` batch of the ``2·n_wf`` segments and one ``nkv_orbit_stage`` per
-    stage, the same bits as the stored mode; ``rmatvec`` then has no orbit to run backwards through and raises."""
+    stage, the same bits as the stored mode; ``rmatvec`` then has no orbit to run backwards through and raises.
+    About a checkpointed orbit ``matvec`` is that side-by-side run and ``rmatvec`` follows
+    :func:`checkpoint_schedule`: ``fused=False`` recomputes a segment, then runs its adjoint; ``fused=True``
+    pairs the adjoint of a segment with the recomputation of the one before it (``nkv_burgers_backward_rhs``);
+    ``fused=None`` takes ``FUSED_DEFAULT``.  All three give the bits of the stored mode; nothing synchronises
+    with the host and nothing is allocated."""
+
+    FUSED_DEFAULT = True
 
     def __init__(self, of: OrbitFlow):
         self.of, self.ctx, self.lin = of, of.ctx, of.lin
@@ -219,7 +344,7 @@ class OrbitPropagator(LinearOperator):
         ru = rB + 8 * seg
         segments = [rB + 8 * f * sv for f in range(2 * nf)]
         wp, ap, tp = lin._w.data_ptr(), of.flow._acc.data_ptr(), of._tacc.data_ptr()
-        s = [of._slot(0, i) for i in range(4)]
+        s = [of._side_slot(i) for i in range(4)]
         of._project(of._q0.data_ptr(), s[0])
         for n in range(self.nsteps):
             for i in range(4):
@@ -239,6 +364,9 @@ class OrbitPropagator(LinearOperator):
             self._side_by_side(y)
             return
         self._stored()
+        if of.checkpoint:
+            self._side_by_side(y)
+            return
         wp, tp = self.lin._w.data_ptr(), of._tacc.data_ptr()
         for n in range(self.nsteps):
             self._linconv(of._slot(n, 0), y.ptr, False)
@@ -250,14 +378,11 @@ class OrbitPropagator(LinearOperator):
             self._linconv(of._slot(n, 3), wp, False)
             self._rk4(None, 0.0, dt / 6, False, None, y.ptr, zero_rest=True)
 
-    def rmatvec(self, x: NekVector, y: NekVector) -> None:
+    def _adjoint_steps(self, steps, y: NekVector) -> None:
+        """The adjoint of the base steps ``steps`` (descending) about their stage states, in place in ``y``."""
         of, dt = self.of, self.dt
-        if not of.store:
-            raise RuntimeError("the adjoint runs backwards through the stored orbit: build the OrbitFlow with store=True")
-        self._stored()
-        self.lin.project(x, y)
         wp, tp = self.lin._w.data_ptr(), of._tacc.data_ptr()
-        for n in reversed(range(self.nsteps)):
+        for n in steps:
             self._linconv(of._slot(n, 3), y.ptr, True)
             self._rk4(y.ptr, dt / 2, dt / 6, True, wp, tp)
             self._linconv(of._slot(n, 2), wp, True)
@@ -267,5 +392,58 @@ class OrbitPropagator(LinearOperator):
             self._linconv(of._slot(n, 0), wp, True)
             self._rk4(None, 0.0, dt / 6, False, None, y.ptr, zero_rest=True)
 
+    def _paired_step(self, n: int, m: int, y: NekVector) -> None:
+        """The adjoint of step n about its window and base step m into the other window, stage by stage in the
+        same launches.  The (a, b) of an adjoint stage are the base stage's, so ``nkv_orbit_stage`` serves both
+        halves: its base half is stage i of step m, its tangent half adjoint stage i about s_{4−i}(n)."""
+        of, lin, ctx, lay = self.of, self.lin, self.ctx, self.ctx.layout
+        sv, nf = lay.sv, lay.n_wf
+        rX = of._r2.data_ptr()
+        ru = rX + 8 * of._seg
+        segments = [rX + 8 * f * sv for f in range(2 * nf)]
+        wp, ap, tp = lin._w.data_ptr(), of.flow._acc.data_ptr(), of._tacc.data_ptr()
+        S = [of._slot(n, i) for i in range(4)]
+        X = [of._slot(m, i) for i in range(4)]
+        for i in range(4):
+            ctx.call("nkv_burgers_backward_rhs", lay.lx1, lay.ldim, lin.D.data_ptr(), lin.w.data_ptr(), *lin._xyz_ptrs(),
+                     X[i], sv, S[3 - i], sv, lin.kappa.data_ptr(), y.ptr if i == 0 else wp, nf, sv, rX, sv, ru, sv,
+                     ctx.stream)
+            average_segments(lin.face_average, segments)
+            if i < 3:
+                of._stage(m, i, X[0], rX, ap, X[i + 1], tan=(y.ptr, ru, wp, tp))
+            else:   # (bit 0 is never set: the base half ends in the orbit buffer)
+                of._stage(m, i, None, rX, of._next(m), None, zero_rest=2, tan=(None, ru, None, y.ptr))
 
-__all__ = ["OrbitFlow", "OrbitPropagator"]
+    def _pair(self, ja: int, jr: int, k: int, y: NekVector) -> None:
+        of = self.of
+        start, end = of._span(ja)
+        if of._holds(jr):           # nothing to recompute next to this adjoint
+            self._adjoint_steps(range(end - 1, start - 1, -1), y)
+            return
+        of._wtag[jr & 1] = None
+        first = of._span(jr)[0]
+        for t in range(k):
+            self._paired_step(end - 1 - t, first + t, y)
+        of._wtag[jr & 1] = (of._run, jr)
+        of._recompute(jr, k)        # the steps of jr without a partner (a shorter last segment)
+
+    def rmatvec(self, x: NekVector, y: NekVector, fused=None) -> None:
+        of = self.of
+        if not of.store:
+            raise RuntimeError("the adjoint runs backwards through the stored orbit: build the OrbitFlow with store=True")
+        self._stored()
+        self.lin.project(x, y)
+        if not of.checkpoint:
+            self._adjoint_steps(range(self.nsteps - 1, -1, -1), y)
+            return
+        for op in of._plan[bool(self.FUSED_DEFAULT if fused is None else fused)]:
+            if op[0] == "recompute":
+                of._recompute(op[1])
+            elif op[0] == "adjoint":
+                start, end = of._span(op[1])
+                self._adjoint_steps(range(end - 1, start - 1, -1), y)
+            else:
+                self._pair(op[1], op[2], op[3], y)
+
+
+__all__ = ["OrbitFlow", "OrbitPropagator", "auto_checkpoint", "checkpoint_schedule"]
