@@ -952,6 +952,43 @@ int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, co
                      const double* u_re, const double* u_im, int nfld, int64_t u_stride, double* r_re, double* r_im,
                      int64_t r_stride, int adjoint, void* stream);
 
+/* ---- the pressure operators of an incompressible flow and the CG of its projection -------------------
+ * Nek5000's opdiv / opgradt / cdabdtp (navier1.f) on the P_N - P_{N-2} pair: the pressure lives on lx2 = lx1 - 2
+ * Gauss-Legendre points per direction and element, element-discontinuous (nel lx2^ldim values, elements in
+ * order, the first direction fastest).  D, w^, I^: the GLL derivative (lx1 x lx1, row-major), the tensor product
+ * of the Gauss weights gw (lx2) and of the Lagrange interpolation interp (lx2 x lx1, row-major) from the GLL to
+ * the Gauss points; g[d][a]: the cofactors nkv_gradm1 forms.  Conventions, the tiling, the treatment of bad
+ * arguments and of empty shards: as for the advection-diffusion entries.  lx1 = 3 .. 10.  No atomics, no
+ * contraction; any element sub-range (pointers offset, n_v shortened) gives the bits of the whole.
+ *
+ * nkv_pressure_div:   out[e,q] = w^_q I^( sum_{d<ldim} sum_a g[d][a] D_a (mult u_d) )[e,q]: the weak divergence
+ *   of the ldim fields at u + d*u_stride, each multiplied pointwise by mult (n_v values) when mult is not NULL.
+ *   With pv (a pressure-mesh vector) and partials given, workgroup b also writes its share of pv.out, sum out
+ *   and sum pv to partials[b], partials[NKV_PRESSURE_PARTIALS + b], partials[2 NKV_PRESSURE_PARTIALS + b]
+ *   (b < at most NKV_PRESSURE_PARTIALS workgroups, a fixed count for a given n_v; other slots are not touched).
+ * nkv_pressure_gradt: t_d = sum_a D_a^T [ g[d][a] I^^T(w^ p) ], the ldim unassembled GLL fields at
+ *   t + d*t_stride: the matrix transpose of nkv_pressure_div.  With res given, p <- first ? res : res + beta p
+ *   is formed on the load and stored back, beta = (sum of the B values at rr_new) / (sum of those at rr_old),
+ *   0 when the denominator is.
+ * nkv_pressure_cg_update: the pointwise third of a CG iteration over n pressure values.  red: the three rows
+ *   of Br partials nkv_pressure_div wrote (Br = NKV_PRESSURE_PARTIALS, or 1 after the caller reduced them over
+ *   ranks); rr_old: Bo partials of r.r.  mu = closed ? sum Ep * inv_n : 0; alpha = r.r / (p.Ep - mu sum p), 0
+ *   when the denominator is;  x <- x + alpha p,  r <- r - alpha (Ep - mu);  workgroup b writes its share of the
+ *   new r.r to rr_out[b] (at most NKV_PRESSURE_PARTIALS workgroups).  init: x <- 0, r <- Ep - mu.
+ *   Every workgroup sums partials in one fixed order: the same input gives the same bits. */
+#define NKV_PRESSURE_PARTIALS 1024
+int nkv_pressure_div(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                     const double* xm, const double* ym, const double* zm, const double* u, int64_t u_stride,
+                     const double* mult, double* out, const double* pv, double* partials, void* stream);
+int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                       const double* xm, const double* ym, const double* zm, double* p, const double* res,
+                       const double* rr_new, const double* rr_old, int B, int first, double* t, int64_t t_stride,
+                       void* stream);
+int nkv_pressure_cg_update(int64_t n, double* x, double* r, const double* p, const double* Ep, const double* red, int Br,
+                           const double* rr_old, int Bo, double inv_n, int closed, int init, double* rr_out,
+                           void* stream);
+int nkv_pressure_partials(void);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

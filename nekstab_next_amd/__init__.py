@@ -17,7 +17,7 @@ def __getattr__(name):
     for mod in ("vector", "operators", "arnoldi", "krylov_schur", "gmres", "newton", "sensitivity", "lapack",
                 "comm", "synthetic", "lightkrylov", "drivers", "checkpoint", "fld", "boostconv", "seeds", "fixedp",
                 "postproc", "vortex", "forcing", "monitors", "gs", "advdiff", "resolvent", "burgers", "orbit",
-                "_lib"):
+                "pressure", "incompressible", "_lib"):
         if name == mod:
             return importlib.import_module(f".{mod}", __name__)
     if name in ("SFD", "TDF"):   # the fixed-point forcing classes (fixedp.py)
@@ -34,4 +34,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".burgers", __name__), name)
     if name in ("OrbitFlow", "OrbitPropagator", "checkpoint_schedule"):   # the time-periodic base flow and its tangent (orbit.py)
         return getattr(importlib.import_module(".orbit", __name__), name)
+    if name == "DivergenceFreeProjector":   # the pressure solve of the divergence-free projection (pressure.py)
+        return getattr(importlib.import_module(".pressure", __name__), name)
+    if name in ("IncompressibleFlow", "LinearisedNavierStokes"):   # the incompressible flow over it (incompressible.py)
+        return getattr(importlib.import_module(".incompressible", __name__), name)
     raise AttributeError(name)

@@ -170,6 +170,11 @@ _SIGNATURES = {
                                    c_double, _P, _P, c_int64, c_int, c_int, _P]),
     "nkv_linconv_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int64, _P, c_int64,
                                 c_int, _P]),
+    "nkv_pressure_div": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "nkv_pressure_gradt": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int64,
+                                   _P]),
+    "nkv_pressure_cg_update": (c_int, [c_int64, _P, _P, _P, _P, _P, c_int, _P, c_int, c_double, c_int, c_int, _P, _P]),
+    "nkv_pressure_partials": (c_int, []),
     "nkv_rk4_stage": (c_int, [_L, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_double, c_double, c_int, _P, c_int64,
                               _P, c_int64, _P, c_int64, c_int, c_int, _P]),
     "nkv_burgers_tangent_rhs": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int64, _P,

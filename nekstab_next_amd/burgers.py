@@ -98,7 +98,7 @@ class ViscousBurgers:
                  face_average="auto"):
         lay = ctx.layout
         zero = [np.zeros(lay.n_v) for _ in range(lay.n_wf)]
-        self.lin = LinearisedConvection(ctx, coords, zero, kappa, dt, nsteps, mask=mask, face_average=face_average)
+        self.lin = self._make_lin(ctx, coords, zero, kappa, dt, nsteps, mask, face_average)
         self.ctx, self.dt, self.nsteps, self.tau = ctx, self.lin.dt, self.lin.nsteps, self.lin.tau
         self.bm1, self.mask, self.minv = self.lin.bm1, self.lin.mask, self.lin.minv
         f64 = dict(dtype=torch.float64, device=ctx.device)
@@ -110,6 +110,10 @@ class ViscousBurgers:
         self._forced = False
         if forcing is not None:
             self.set_forcing(forcing)
+
+    def _make_lin(self, ctx, coords, base, kappa, dt, nsteps, mask, face_average) -> LinearisedConvection:
+        """The linearised operator the flow owns (a subclass may own a subclass of it)."""
+        return LinearisedConvection(ctx, coords, base, kappa, dt, nsteps, mask=mask, face_average=face_average)
 
     # ---- forcing ----
     def _load(self, rows, dst: NekVector) -> None:

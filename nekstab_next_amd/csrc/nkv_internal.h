@@ -33,6 +33,9 @@
 //                     complex Horner stage of the rotating-frame resolvent (re / im halves, forcing inside);
 //                     the convection linearised about a base state (production term, forward and adjoint) and
 //                     the classical RK4 stage of the viscous Burgers flow
+//   pressure.hip      the pressure operators of the incompressible flow on the P_N - P_{N-2} pair: weak divergence
+//                     onto the Gauss mesh, its transpose, and the pointwise third of the CG iteration of the
+//                     divergence-free projection (deterministic partials, scalars on the device)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,0 +1,540 @@
+// pressure.hip — the P_N - P_{N-2} pressure operators of an incompressible flow on the GLL mesh and the fused
+// conjugate-gradient iteration of the divergence-free projection behind pressure.DivergenceFreeProjector
+// (Nek5000's opdiv / opgradt / cdabdtp, navier1.f).  Notation of advdiff.hip: g[d][a] the cofactors of
+// k_gradm1 (geometric_factors_jac), D_a the GLL line derivative; lx2 = lx1 - 2 Gauss-Legendre points per
+// direction carry the pressure, I (lx2 x lx1) interpolates from the GLL to the Gauss points, I^ is its tensor
+// product and w^ the tensor product of the Gauss weights.  The pressure is element-discontinuous
+// (nel lx2^ldim values), nothing on its mesh is assembled.
+//   k_pressure_div:    (D u)[e,q]  = w^_q I^( sum_{d<ldim} sum_a g[d][a] D_a (m u_d) )[e,q]      (m: optional)
+//   k_pressure_gradt:  (D^T p)_d   = sum_a D_a^T [ g[d][a] I^^T(w^ p) ]                         (unassembled)
+// two matrices that are transposes of each other.  Both tile like k_advdiff_rhs (whole elements per workgroup,
+// one GLL point per thread, factors formed once per group) and interpolate by sum factorisation, one direction
+// at a time through LDS.  No atomics, no contraction; element-local, so any element sub-range gives the bits
+// of the whole.
+// With E = D minv dsavg D^T the iteration of unpreconditioned CG on E (or on Z E Z, Z = I - 1 1^T / n, when
+// the constant is a null vector) is three launches and one dsavg batch:
+//   k_pressure_gradt      forms p = r + beta p on its load (beta from the partials of r.r) and writes D^T p
+//   k_pressure_div        applies minv on its load and emits the partials of p.Ep, sum Ep and sum p
+//   k_pressure_cg_update  alpha from those partials; x += alpha p, r -= alpha (Ep - mean Ep); partials of r.r
+// Every scalar stays on the device: a producer writes one partial per workgroup into a fixed slot, and every
+// workgroup of the consumer sums the slots in the same fixed order (cg_scalar), so all of them hold the same
+// bits and the same input gives the same bits run to run.
+#include "nkv_internal.h"
+
+namespace {
+
+constexpr int kPB = NKV_PRESSURE_PARTIALS;   // partial slots per reduced quantity
+static_assert(kPB % 64 == 0, "cg_scalar strides the slots by one wave");
+
+// The sum of B partials in a fixed order, the same bits in every workgroup of every kernel that calls it:
+// the first wave strides over the slots, then a fixed exchange pattern.  Every thread of the block returns
+// the sum.  slot: one LDS double per call site.
+__device__ __forceinline__ double cg_scalar(const double* __restrict__ part, int B, double* slot) {
+    if (threadIdx.x < 64) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < B; b += 64) s += part[b];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) *slot = s;
+    }
+    __syncthreads();
+    return *slot;
+}
+
+// Block-wide sums of three per-thread values (whole waves, up to kMaxWaves): waves in ascending order.
+// Valid in thread 0.  red: 3 * kMaxWaves doubles of LDS.
+__device__ __forceinline__ void block_sum3(double& a, double& b, double& c, double* red) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    c = wave_sum(c);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) {
+        red[wave] = a;
+        red[kMaxWaves + wave] = b;
+        red[2 * kMaxWaves + wave] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = red[0];
+        b = red[kMaxWaves];
+        c = red[2 * kMaxWaves];
+        for (int w = 1; w < nw; ++w) {
+            a += red[w];
+            b += red[kMaxWaves + w];
+            c += red[2 * kMaxWaves + w];
+        }
+    }
+}
+
+// The head of the LDS both tiled kernels carve: D, the interpolation matrix, the Gauss weights and the
+// reduction scratch (an even number of doubles: the tiles behind it stay 16-byte aligned).
+template <int NX>
+constexpr int head_doubles() {
+    return NX * NX + (NX - 2) * NX + (NX - 2) + (NX & 1) + 3 * kMaxWaves + 2;
+}
+template <int LDIM, int NX>
+constexpr int pressure_pts() { return LDIM == 3 ? (NX - 2) * (NX - 2) * (NX - 2) : (NX - 2) * (NX - 2); }
+
+template <int NX>
+struct Head {
+    double *D, *I, *gw, *red, *tiles;
+    __device__ __forceinline__ Head(double* lds, const double* Dg, const double* Ig, const double* gwg) {
+        constexpr int M = NX - 2;
+        D = lds;
+        I = D + NX * NX;        // I(q, i) at I[q*NX + i]
+        gw = I + M * NX;
+        red = gw + M + (NX & 1);
+        tiles = lds + head_doubles<NX>();
+        for (int t = threadIdx.x; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+        for (int t = threadIdx.x; t < M * NX; t += blockDim.x) I[t] = Ig[t];
+        for (int t = threadIdx.x; t < M; t += blockDim.x) gw[t] = gwg[t];
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// The weak divergence on the pressure mesh.  Per element group: stage the coordinates, form the factors,
+// stage the ldim velocity components over the coordinate tiles (times m when given), take the line sums
+//   dv = sum_d (g[d][0] u_d,r + g[d][1] u_d,s [+ g[d][2] u_d,t])          (jac div u at the GLL point)
+// and interpolate dv to the Gauss points along r, then s[, then t], ping-pong between two of the tiles; the
+// thread that owns Gauss point q of its element scales by w^_q and stores.  With pv given the same thread
+// accumulates pv.out, sum out and sum pv, and the workgroup writes the three partials into its slots.
+// LDS: head + ldim nt doubles.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_div(
+    int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm,
+    const double* __restrict__ u, int64_t u_stride, const double* __restrict__ mult, double* __restrict__ out,
+    const double* __restrict__ pv, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int M = NX - 2;
+    constexpr int ppts = pressure_pts<LDIM, NX>();
+    const int nt = epb * pts;
+    const Head<NX> h(lds, Dg, Ig, gwg);
+    const double* I = h.I;
+    double* X = h.tiles;
+    double* Y = X + nt;
+    double* Z = Y + nt;                      // 3-D only
+    const int tid = threadIdx.x;
+    const TilePoint<LDIM, NX> q(h.D, tid, nt);
+    const int le = tid / pts, rr = tid - le * pts;
+    const int eb = le * pts;                 // this thread's element inside the tiles (used below tid < nt only)
+    const bool intile = tid < nt;
+    double s_pe = 0.0, s_e = 0.0, s_p = 0.0;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = intile && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and the head is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        __syncthreads();       // every lane has formed its factors: the tiles are free
+        if (live) {
+            const double m = mult ? mult[p] : 1.0;
+            double* tiles[3] = {X, Y, Z};
+#pragma unroll
+            for (int d = 0; d < LDIM; ++d) {
+                const double v = u[d * u_stride + p];
+                tiles[d][tid] = mult ? m * v : v;
+            }
+        }
+        __syncthreads();
+        double dv = 0.0;
+        {
+            const double* tiles[3] = {X, Y, Z};
+#pragma unroll
+            for (int d = 0; d < LDIM; ++d) {
+                double ur, us, ut;
+                line_sums<LDIM, NX>(q, tiles[d], ur, us, ut);
+                double t = g[d][0] * ur + g[d][1] * us;
+                if constexpr (LDIM == 3) t = t + g[d][2] * ut;
+                dv = d == 0 ? t : dv + t;
+            }
+        }
+        __syncthreads();       // the velocity tiles are read
+        if (intile) X[tid] = dv;
+        __syncthreads();
+        // along r: X(i, j, k) -> Y(a, j, k), a < M
+        constexpr int n1 = LDIM == 3 ? M * NX * NX : M * NX;
+        if (intile && rr < n1) {
+            const int a = rr % M, row = rr / M;          // row = j + NX k
+            const double* src = X + eb + row * NX;
+            double acc = I[a * NX] * src[0];
+#pragma unroll 2
+            for (int m = 1; m < NX; ++m) acc = acc + I[a * NX + m] * src[m];
+            Y[eb + rr] = acc;
+        }
+        __syncthreads();
+        // along s: Y(a, j, k) -> (a, b, k)
+        constexpr int n2 = LDIM == 3 ? M * M * NX : M * M;
+        double val = 0.0;
+        if (intile && rr < n2) {
+            const int a = rr % M, b = (rr / M) % M, k = rr / (M * M);
+            const double* src = Y + eb + a + M * NX * k;
+            double acc = I[b * NX] * src[0];
+#pragma unroll 2
+            for (int m = 1; m < NX; ++m) acc = acc + I[b * NX + m] * src[M * m];
+            if constexpr (LDIM == 3) X[eb + rr] = acc;
+            val = acc;
+        }
+        if constexpr (LDIM == 3) {
+            __syncthreads();
+            // along t: X(a, b, k) -> (a, b, c)
+            if (intile && rr < ppts) {
+                const int c = rr / (M * M), ab = rr - c * M * M;
+                const double* src = X + eb + ab;
+                double acc = I[c * NX] * src[0];
+#pragma unroll 2
+                for (int m = 1; m < NX; ++m) acc = acc + I[c * NX + m] * src[M * M * m];
+                val = acc;
+            }
+        }
+        if (live && rr < ppts) {
+            const int a = rr % M, b = (rr / M) % M, c = LDIM == 3 ? rr / (M * M) : 0;
+            const double wab = h.gw[a] * h.gw[b];
+            const double wq = LDIM == 3 ? wab * h.gw[c] : wab;
+            const double o = wq * val;
+            const int64_t pp = (e0 + le) * ppts + rr;
+            out[pp] = o;
+            if (pv) {
+                const double pe = pv[pp];
+                s_pe += pe * o;
+                s_e += o;
+                s_p += pe;
+            }
+        }
+    }
+    if (partials) {
+        block_sum3(s_pe, s_e, s_p, h.red);
+        if (tid == 0) {
+            partials[blockIdx.x] = s_pe;
+            partials[kPB + blockIdx.x] = s_e;
+            partials[2 * kPB + blockIdx.x] = s_p;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The transposed operator.  Per element group: stage the coordinates and, by the thread that owns Gauss point
+// q, w^_q p_q (with res given, p <- first ? res : res + beta p is formed here and stored back, beta =
+// rr_new / rr_old from the partials); interpolate transposed along t[, then s], then r back to the GLL points
+// (the factors are formed meanwhile); then for every direction d write the fluxes g[d][a] s over the
+// coordinate tiles and take the transposed line sums of k_advdiff_rhs.  LDS: head + (ldim + 2) nt doubles,
+// 41,904 bytes at lx1 = 10 in 3-D.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
+    int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm, double* pin,
+    const double* __restrict__ res, const double* __restrict__ rr_new, const double* __restrict__ rr_old, int B,
+    int first, double* __restrict__ t, int64_t t_stride) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int sj = NX, sk = NX * NX;
+    constexpr int M = NX - 2;
+    constexpr int ppts = pressure_pts<LDIM, NX>();
+    const int nt = epb * pts;
+    const Head<NX> h(lds, Dg, Ig, gwg);
+    const double* I = h.I;
+    double* X = h.tiles;
+    double* Y = X + nt;
+    double* Z = Y + nt;                      // 3-D only
+    double* A = LDIM == 3 ? Z + nt : Z;
+    double* Bt = A + nt;
+    const int tid = threadIdx.x;
+    double beta = 0.0;
+    if (res && !first) {   // (uniform over the grid)
+        const double num = cg_scalar(rr_new, B, h.red), den = cg_scalar(rr_old, B, h.red + 1);
+        beta = den != 0.0 ? num / den : 0.0;
+    }
+    const TilePoint<LDIM, NX> q(h.D, tid, nt);
+    const int le = tid / pts, rr = tid - le * pts;
+    const int eb = le * pts;
+    const bool intile = tid < nt;
+    const int pi = rr % NX, pj = (rr / NX) % NX, pk = LDIM == 3 ? rr / (NX * NX) : 0;
+    const double* Dci = h.D + pi;            // this point's columns of D: D(m, i) at Dci[m*NX]
+    const double* Dcj = h.D + pj;
+    const double* Dck = h.D + pk;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = intile && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and the head is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+            if (rr < ppts) {
+                const int a = rr % M, b = (rr / M) % M, c = LDIM == 3 ? rr / (M * M) : 0;
+                const double wab = h.gw[a] * h.gw[b];
+                const double wq = LDIM == 3 ? wab * h.gw[c] : wab;
+                const int64_t pp = (e0 + le) * ppts + rr;
+                double v;
+                if (res) {
+                    v = first ? res[pp] : res[pp] + beta * pin[pp];
+                    pin[pp] = v;
+                } else {
+                    v = pin[pp];
+                }
+                A[eb + rr] = wq * v;
+            }
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        double* S1 = A;        // the tile the transposed s pass reads
+        double* S2 = Bt;       // ... and writes
+        if constexpr (LDIM == 3) {
+            // along t, transposed: A(a, b, c) -> Bt(a, b, k)
+            if (intile && rr < M * M * NX) {
+                const int k = rr / (M * M), ab = rr - k * M * M;
+                const double* src = A + eb + ab;
+                double acc = I[k] * src[0];
+#pragma unroll 2
+                for (int c = 1; c < M; ++c) acc = acc + I[c * NX + k] * src[M * M * c];
+                Bt[eb + rr] = acc;
+            }
+            __syncthreads();
+            S1 = Bt;
+            S2 = A;
+        }
+        // along s, transposed: S1(a, b, k) -> S2(a, j, k)
+        constexpr int n2 = LDIM == 3 ? M * NX * NX : M * NX;
+        if (intile && rr < n2) {
+            const int a = rr % M, j = (rr / M) % NX, k = rr / (M * NX);
+            const double* src = S1 + eb + a + M * M * k;
+            double acc = I[j] * src[0];
+#pragma unroll 2
+            for (int b = 1; b < M; ++b) acc = acc + I[b * NX + j] * src[M * b];
+            S2[eb + rr] = acc;
+        }
+        __syncthreads();
+        // along r, transposed: S2(a, j, k) -> the GLL point (i, j, k)
+        double s = 0.0;
+        if (intile) {
+            const double* src = S2 + eb + M * (rr / NX);
+            s = I[pi] * src[0];
+#pragma unroll 2
+            for (int a = 1; a < M; ++a) s = s + I[a * NX + pi] * src[a];
+        }
+        // (every lane formed its factors before the barriers above: the coordinate tiles are free)
+#pragma unroll
+        for (int d = 0; d < LDIM; ++d) {
+            if (d > 0) __syncthreads();   // the previous direction's fluxes are read
+            if (intile) {
+                X[tid] = g[d][0] * s;
+                Y[tid] = g[d][1] * s;
+                if constexpr (LDIM == 3) Z[tid] = g[d][2] * s;
+            }
+            __syncthreads();
+            if (live) {
+                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
+#pragma unroll 2
+                for (int m = 1; m < NX; ++m) {
+                    tr = tr + Dci[m * NX] * X[q.ri + m];
+                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
+                }
+                double acc = tr + ts;
+                if constexpr (LDIM == 3) {
+                    double tt = Z[q.ti] * Dck[0];
+#pragma unroll 2
+                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
+                    acc = acc + tt;
+                }
+                t[d * t_stride + p] = acc;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The pointwise third of a CG iteration on the pressure mesh.  Every workgroup forms the scalars from the
+// partials (cg_scalar):  mu = closed ? sum Ep / n : 0,  alpha = r.r / (p.Ep - mu sum p)  (0 when that is 0),
+// then per point, without contraction,
+//   x <- x + alpha p      r <- r - alpha (Ep - mu)
+// and writes its partial of the new r.r into its slot.  init: x <- 0, r <- Ep - mu (the right-hand side with
+// its mean removed), no p.  Thread-to-point map and block sums are fixed: the same bits run to run.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_pressure_cg_update(int64_t n, double* __restrict__ x,
+                                                                 double* __restrict__ r, const double* __restrict__ p,
+                                                                 const double* __restrict__ Ep,
+                                                                 const double* __restrict__ red, int Br,
+                                                                 const double* __restrict__ rr_old, int Bo, double inv_n,
+                                                                 int closed, int init, double* __restrict__ rr_out) {
+#pragma clang fp contract(off)
+    __shared__ double sc[8];
+    const double s_e = closed ? cg_scalar(red + Br, Br, sc) : 0.0;
+    const double mu = s_e * inv_n;
+    double alpha = 0.0;
+    if (!init) {
+        const double p_e = cg_scalar(red, Br, sc + 1), s_p = cg_scalar(red + 2 * (int64_t)Br, Br, sc + 2);
+        const double rr = cg_scalar(rr_old, Bo, sc + 3);
+        const double den = p_e - mu * s_p;
+        alpha = den != 0.0 ? rr / den : 0.0;
+    }
+    double s = 0.0;
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += step) {
+        double rv;
+        if (init) {
+            x[i] = 0.0;
+            rv = Ep[i] - mu;
+        } else {
+            x[i] = x[i] + alpha * p[i];
+            rv = r[i] - alpha * (Ep[i] - mu);
+        }
+        r[i] = rv;
+        s += rv * rv;
+    }
+    s = block_sum(s, sc + 4);
+    if (threadIdx.x == 0) rr_out[blockIdx.x] = s;
+}
+
+template <int LDIM, int NX>
+void launch_div(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
+                const double* zm, const double* u, int64_t u_stride, const double* mult, double* out, const double* pv,
+                double* partials, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)LDIM * epb * pts);
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, kPB);
+    hipLaunchKernelGGL((k_pressure_div<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I, gw,
+                       xm, ym, zm, u, u_stride, mult, out, pv, partials);
+}
+
+template <int LDIM, int NX>
+void launch_gradt(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
+                  const double* zm, double* p, const double* res, const double* rr_new, const double* rr_old, int B,
+                  int first, double* t, int64_t t_stride, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)(LDIM + 2) * epb * pts);
+    static_assert(sizeof(double) * (head_doubles<10>() + 5 * 1000) <= 65536, "dynamic LDS within 64 KiB at lx1 = 10");
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 4 * kPB);
+    hipLaunchKernelGGL((k_pressure_gradt<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
+                       gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride);
+}
+
+int check_pressure_args(const char* who, const nkv_layout* L, int lx1, int ldim, const double* zm) {
+    if (lx1 < 3 && lx1 >= 0 && (ldim == 2 || ldim == 3))
+        return fail(NKV_EINVAL, "%s: lx1=%d: the pressure mesh has lx1 - 2 points per direction, lx1 >= 3", who, lx1);
+    return check_mesh_args(who, L, lx1, ldim, zm);
+}
+
+// One switch case per supported lx1 of the pressure kernels (lx2 = lx1 - 2 >= 1).
+#define NKV_PR_CASES(CALL) CALL(3) CALL(4) CALL(5) CALL(6) CALL(7) CALL(8) CALL(9) CALL(10)
+
+}  // namespace
+
+extern "C" {
+
+int nkv_pressure_div(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                     const double* xm, const double* ym, const double* zm, const double* u, int64_t u_stride,
+                     const double* mult, double* out, const double* pv, double* partials, void* stream) {
+    static const char who[] = "pressure_div";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch (its partial slots stay as they are)
+    CHECK(check_pressure_args(who, L, lx1, ldim, zm));
+    if (u_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: stride u_stride=%lld below n_v=%lld", who, (long long)u_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(interp, who, "interp"));
+    CHECK(need(gw, who, "gw"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(u, who, "u"));
+    CHECK(need(out, who, "out"));
+    if (!pv != !partials) return fail(NKV_EINVAL, "%s: pv and partials are both NULL or neither", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_PR_DIV(NX)                                                                                        \
+    case NX:                                                                                                  \
+        if (ldim == 3) launch_div<3, NX>(nel, D, interp, gw, xm, ym, zm, u, u_stride, mult, out, pv, partials, st); \
+        else launch_div<2, NX>(nel, D, interp, gw, xm, ym, zm, u, u_stride, mult, out, pv, partials, st);     \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_DIV) }
+#undef NKV_PR_DIV
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                       const double* xm, const double* ym, const double* zm, double* p, const double* res,
+                       const double* rr_new, const double* rr_old, int B, int first, double* t, int64_t t_stride,
+                       void* stream) {
+    static const char who[] = "pressure_gradt";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
+    CHECK(check_pressure_args(who, L, lx1, ldim, zm));
+    if (t_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: stride t_stride=%lld below n_v=%lld", who, (long long)t_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(interp, who, "interp"));
+    CHECK(need(gw, who, "gw"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    CHECK(need(p, who, "p"));
+    CHECK(need(t, who, "t"));
+    if (res && !first) {
+        CHECK(need(rr_new, who, "rr_new"));
+        CHECK(need(rr_old, who, "rr_old"));
+        if (B < 1 || B > kPB) return fail(NKV_EINVAL, "%s: B=%d outside 1..%d", who, B, kPB);
+    }
+    if (res == p) return fail(NKV_EINVAL, "%s: res is p", who);
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    hipStream_t st = S(stream);
+#define NKV_PR_GT(NX)                                                                                                 \
+    case NX:                                                                                                          \
+        if (ldim == 3)                                                                                                \
+            launch_gradt<3, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, st);   \
+        else                                                                                                          \
+            launch_gradt<2, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, st);   \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_GT) }
+#undef NKV_PR_GT
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_cg_update(int64_t n, double* x, double* r, const double* p, const double* Ep, const double* red, int Br,
+                           const double* rr_old, int Bo, double inv_n, int closed, int init, double* rr_out,
+                           void* stream) {
+    static const char who[] = "pressure_cg_update";
+    if (n < 0) return fail(NKV_EINVAL, "%s: n=%lld", who, (long long)n);
+    CHECK(need(rr_out, who, "rr_out"));
+    if (n > 0) {
+        CHECK(need(x, who, "x"));
+        CHECK(need(r, who, "r"));
+        CHECK(need(Ep, who, "Ep"));
+    }
+    if (!init) {
+        CHECK(need(red, who, "red"));
+        CHECK(need(rr_old, who, "rr_old"));
+        if (n > 0) CHECK(need(p, who, "p"));
+        if (Bo < 1 || Bo > kPB) return fail(NKV_EINVAL, "%s: Bo=%d outside 1..%d", who, Bo, kPB);
+    }
+    if (closed) CHECK(need(red, who, "red"));
+    if ((closed || !init) && (Br < 1 || Br > kPB)) return fail(NKV_EINVAL, "%s: Br=%d outside 1..%d", who, Br, kPB);
+    if (!std::isfinite(inv_n)) return fail(NKV_EINVAL, "%s: inv_n=%g", who, inv_n);
+    // (an empty shard still launches one workgroup: it writes a zero partial)
+    const int grid = grid_for(n, kPB);
+    hipLaunchKernelGGL(k_pressure_cg_update, dim3(grid), dim3(kThreads), 0, S(stream), n, x, r, p, Ep, red, Br, rr_old, Bo,
+                       inv_n, closed, init, rr_out);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_partials(void) { return kPB; }
+
+}  // extern "C"

@@ -1,0 +1,126 @@
+"""An incompressible flow on the GLL mesh, its exact linearisation and its exact discrete adjoint: the viscous
+Burgers flow of :mod:`~nekstab_next_amd.burgers` with the divergence-free projection of
+:mod:`~nekstab_next_amd.pressure` behind every right-hand side.
+
+Reference: nekStab's operators are incompressible Navier–Stokes (its state vector carries ``pr`` on the ``lx2``
+mesh for that reason; newton_krylov.f90:1-166, matvec.f90:520-571).  The Burgers right-hand sides
+(``nkv_advdiff_rhs`` with ``U = u``, ``nkv_linconv_rhs``) are the Navier–Stokes convective and viscous terms;
+with ``P`` the projector onto the discretely divergence-free velocities (``DivergenceFreeProjector``; scalars
+are not touched) and the notation of the Burgers module:
+
+    N(q)    = P( minv · dsavg(r(q; U = q_vel)) ) + g            (g = P Π forcing, projected once)
+    Φ(q)    = RK4^nsteps(P Π q)
+    matvec:  y = p(dt · P L_B)^nsteps P Π x,      rmatvec:  y = p(dt · P L_B†)^nsteps P Π x
+
+``P`` is self-adjoint in the ``bm1`` inner product and ``P (L†P)^k = (P L†)^k P``, so ``matvec`` and
+``rmatvec`` are adjoints of each other up to the CG tolerance.  At a steady state every RK4 stage equals the
+state, and the Jacobian of ``Φ`` there is exactly the linear operator.  ``newton_krylov``, ``krylov_schur``,
+``LegacyMatvec(3.2, ·)``, ``svds`` and ``transient_growth_analysis`` run on these unchanged.
+
+Each stage forms ``k = minv · r`` with ``nkv_advdiff_stage``, projects its velocity rows in place (a CG solve:
+pressure.py) and closes with the parent's stage kernel, the mask standing in for ``minv``.  ``OrbitFlow`` and
+the resolvents drive the right-hand sides and their own stages and would skip the projection: they refuse
+these classes.
+"""
+from __future__ import annotations
+
+import torch
+
+from .burgers import LinearisedConvection, ViscousBurgers
+from .pressure import DivergenceFreeProjector
+from .vector import NekContext, NekVector
+
+
+class LinearisedNavierStokes(LinearisedConvection):
+    """``y = p(dt · P L_B)^nsteps P Π x`` and its adjoint about a base state ``B`` (module docstring):
+    :class:`LinearisedConvection` with the divergence-free projection behind every right-hand side.  ``tol``,
+    ``maxiter``, ``check_every``, ``closed``: the projector's (``self.projector``); everything else as in the
+    parent."""
+
+    def __init__(self, ctx: NekContext, coords: dict, base, kappa, dt: float, nsteps: int, mask=None,
+                 face_average="auto", tol: float = 1e-12, maxiter: int | None = None, check_every: int = 8,
+                 closed="auto"):
+        super().__init__(ctx, coords, base, kappa, dt, nsteps, mask=mask, face_average=face_average)
+        lay = ctx.layout
+        self.projector = DivergenceFreeProjector(ctx, tol=tol, maxiter=maxiter, check_every=check_every, closed=closed,
+                                                 operator=self)
+        self._k = torch.zeros(lay.n_wf * lay.sv + 2, dtype=torch.float64, device=ctx.device)
+
+    def _projected_rhs(self) -> int:
+        """k <- P(minv · r) of the averaged right-hand side in ``self._r``; returns its pointer."""
+        kp = self._k.data_ptr()
+        self._stage(None, self._minv, self._r.data_ptr(), 1.0, kp)
+        self.projector.project_ptr(kp)
+        return kp
+
+    def rhs(self, x: NekVector, y: NekVector, adjoint: bool = False) -> None:
+        """``y = P L_B x`` (``P L_B† x`` if ``adjoint``); ``x`` is taken as it is."""
+        super().rhs(x, y, adjoint)
+        self.projector.project_ptr(y.ptr)
+
+    def project(self, x: NekVector, y: NekVector | None = None) -> NekVector:
+        """``y = P Π x`` (in place when ``y`` is None); pressure and time of ``y`` are zeroed."""
+        y = super().project(x, y)
+        self.projector.project_ptr(y.ptr)
+        return y
+
+    def _propagate(self, x: NekVector, y: NekVector, adjoint: bool) -> None:
+        self.project(x, y)
+        wp = self._w.data_ptr()
+        for _ in range(self.nsteps):
+            src = y.ptr
+            for s in (4, 3, 2):
+                self._local_rhs(src, adjoint)
+                self._stage(y.ptr, self.mask, self._projected_rhs(), self.dt / s, wp)
+                src = wp
+            self._local_rhs(src, adjoint)
+            self._stage(y.ptr, self.mask, self._projected_rhs(), self.dt, y.ptr, zero_rest=True)
+
+
+class IncompressibleFlow(ViscousBurgers):
+    """The incompressible flow ``dq/dt = N(q)`` and its time-``tau`` map ``Φ`` (module docstring):
+    :class:`ViscousBurgers` with ``k_i = P(minv · dsavg r(s_i)) + g`` in every stage and ``g`` projected by
+    ``P Π`` once.  ``linearized(q)`` returns the :class:`LinearisedNavierStokes` the flow owns.  ``tol``,
+    ``maxiter``, ``check_every``, ``closed``: the projector's (``self.projector``)."""
+
+    def __init__(self, ctx: NekContext, coords: dict, kappa, dt: float, nsteps: int, forcing=None, mask=None,
+                 face_average="auto", tol: float = 1e-12, maxiter: int | None = None, check_every: int = 8,
+                 closed="auto"):
+        self._projector_args = dict(tol=tol, maxiter=maxiter, check_every=check_every, closed=closed)
+        super().__init__(ctx, coords, kappa, dt, nsteps, forcing=forcing, mask=mask, face_average=face_average)
+        self.projector = self.lin.projector
+
+    def _make_lin(self, ctx, coords, base, kappa, dt, nsteps, mask, face_average):
+        return LinearisedNavierStokes(ctx, coords, base, kappa, dt, nsteps, mask=mask, face_average=face_average,
+                                      **self._projector_args)
+
+    def steady_forcing(self, q_target) -> None:
+        """``g = −P N₀(P Π q_target)``, N₀ the unforced unprojected generator: ``P Π q_target`` is then an exact
+        discrete steady state (the solve is deterministic, so ``N(P Π q_target)`` is ``a − a`` point by point)."""
+        lin = self.lin
+        self._load(q_target, self._tmp)
+        lin.project(self._tmp)
+        self._nonlinear_rhs(self._tmp.ptr)
+        lin._stage(None, lin.mask, lin._projected_rhs(), -1.0, self._g.data_ptr())
+        self._forced = True
+
+    def _rk4(self, v_ptr, a: float, b: float, first: bool, w_ptr, out_ptr: int, zero_rest: bool = False) -> None:
+        ctx, lay, lin = self.ctx, self.ctx.layout, self.lin
+        sv = lay.sv
+        ctx.call("nkv_rk4_stage", v_ptr, sv, lin.mask.data_ptr(), lin._projected_rhs(), sv,
+                 self._g.data_ptr() if self._forced else None, sv, float(a), float(b), int(first),
+                 self._acc.data_ptr(), sv, w_ptr, sv, out_ptr, sv, lay.n_wf, int(zero_rest), ctx.stream)
+
+
+def refuse_incompressible(who: str, model) -> None:
+    """Raise the ``ValueError`` of a class that drives the right-hand sides and its own stages, and so would
+    silently skip the projection of an :class:`IncompressibleFlow` or a :class:`LinearisedNavierStokes`."""
+    if isinstance(model, (IncompressibleFlow, LinearisedNavierStokes)) or \
+            isinstance(getattr(model, "lin", None), LinearisedNavierStokes):
+        raise ValueError(f"{who}: a {type(model).__name__} is refused: {who} steps with the unprojected right-hand "
+                         f"sides and would silently skip the divergence-free projection of IncompressibleFlow / "
+                         f"LinearisedNavierStokes; orbits and resolvents over the incompressible flow are not "
+                         f"implemented")
+
+
+__all__ = ["IncompressibleFlow", "LinearisedNavierStokes", "refuse_incompressible"]

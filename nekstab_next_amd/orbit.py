@@ -128,6 +128,9 @@ class OrbitFlow:
     mode."""
 
     def __init__(self, flow: ViscousBurgers, cos=None, sin=None, store: bool = True, checkpoint=None):
+        from .incompressible import refuse_incompressible
+
+        refuse_incompressible("OrbitFlow", flow)
         ctx, lay = flow.ctx, flow.ctx.layout
         self.flow, self.lin, self.ctx, self.store = flow, flow.lin, ctx, bool(store)
         self.dt, self.nsteps, self.tau = flow.dt, flow.nsteps, flow.tau

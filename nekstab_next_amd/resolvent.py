@@ -82,6 +82,9 @@ class ResolventOperator(LinearOperator):
 
     def __init__(self, pctx: NekContext, adv: AdvectionDiffusion, omega: float, tol: float = 1e-10, kdim: int = 60,
                  maxiter: int = 20):
+        from .incompressible import refuse_incompressible
+
+        refuse_incompressible(type(self).__name__, adv)
         self._check_model(adv)
         base = adv.ctx.layout
         if not isinstance(pctx.layout, PairLayout) or pctx.layout != pair_layout(base):
