@@ -19,27 +19,124 @@
 // the Horner pass of the coupled resolvent (resolvent.py); and the backward sweep of a checkpointed adjoint,
 // the nonlinear right-hand side of a segment being recomputed and the adjoint one about a stored stage state in
 // one pass (k_burgers_backward_rhs).
+// The tiled kernels are assembled from shared blocks, and the next one should be too.  Device: TileFrame (the carve
+// of the dynamic LDS, D staged, this thread's TilePoint and weight; begin_group stages an element group's
+// coordinates and forms the factors, with the two barriers that takes), physical_gradient (line_sums and
+// physical_derivative of one staged field), field_fluxes (the forward or the adjoint fluxes of one staged field
+// into the tiles, through write_fluxes), presweep_field (one base field of the adjoint's first sweep) and
+// transposed_line_sums (nkv_internal.h).  A kernel keeps its own field loop, its staging and the barriers between
+// them: those are what differs.  Host: check_tiled_entry, spans_meet, dispatch_tile over lx1 x ldim and
+// launch_tiled, which sizes the LDS from the number of field tiles.
+#include <type_traits>
+
 #include "nkv_internal.h"
 
 namespace {
 
-// This thread's point inside its element and the product of its GLL weights.
+// ------------------------------------------------------------------------------------------
+// The building blocks of the tiled kernels.
+// ------------------------------------------------------------------------------------------
+
+// The frame of a tiled kernel: the carve of the dynamic LDS (D, the LDIM coordinate tiles and up to two field
+// tiles behind them: the launch sizes the LDS for the tiles the kernel uses), D staged, this thread's point and
+// weight; and the head of every element group.
 template <int LDIM, int NX>
-struct PointIndex {
-    int i, j, k;
-    __device__ __forceinline__ explicit PointIndex(int tid) {
-        constexpr int pts = tile_pts<LDIM, NX>();
-        const int r = tid % pts;
-        i = r % NX;
-        j = (r / NX) % NX;
-        k = LDIM == 3 ? r / (NX * NX) : 0;
+struct TileFrame {
+    static constexpr int pts = tile_pts<LDIM, NX>();
+    const int tid, nt, le;
+    double* const D;                         // D(i, m) at D[i*NX + m]
+    double* const X;                         // coordinates, then the flux along r
+    double* const Y;                         // ... along s
+    double* const Z;                         // ... along t (3-D only)
+    double* const U;                         // the first field tile (kernels with one or two)
+    double* const Bt;                        // the second field tile (kernels with two)
+    const TilePoint<LDIM, NX> q;
+    double wt;                               // w_i w_j [w_k]
+
+    __device__ __forceinline__ TileFrame(double* lds, int epb, const double* Dg, const double* wg)
+        : tid(threadIdx.x), nt(epb * pts), le(tid / pts), D(lds), X(D + NX * NX), Y(X + nt), Z(Y + nt),
+          U(LDIM == 3 ? Z + nt : Z), Bt(U + nt), q(D, tid, nt) {
+        for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
+        wt = q.weight(wg);
     }
-    __device__ __forceinline__ double weight(const double* w) const {
+
+    // The head of the element group at e0: stage its coordinates, form this point's factors.  Returns whether
+    // this lane owns a point of the group (dead lanes compute garbage they never store); p: that point.
+    __device__ __forceinline__ bool begin_group(int64_t e0, int64_t nel, const double* xm, const double* ym,
+                                                const double* zm, int64_t& p, double (&g)[3][3], double& jac) const {
 #pragma clang fp contract(off)
-        const double wij = w[i] * w[j];
-        return LDIM == 3 ? wij * w[k] : wij;
+        p = e0 * pts + tid;
+        const bool live = tid < nt && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        return live;
     }
 };
+
+// The LDIM physical derivatives of one staged field at this point (line_sums, then physical_derivative).
+template <int LDIM, int NX>
+__device__ __forceinline__ void physical_gradient(const TilePoint<LDIM, NX>& q, const double* T,
+                                                  const double (&g)[3][3], double jacmi, double (&dT)[LDIM]) {
+#pragma clang fp contract(off)
+    double tr, ts, tt;
+    line_sums<LDIM, NX>(q, T, tr, ts, tt);
+#pragma unroll
+    for (int d = 0; d < LDIM; ++d) dT[d] = physical_derivative<LDIM>(g, jacmi, d, tr, ts, tt);
+}
+
+// The flux writer: F_a = sum_d (g[d][a] / jac) G_d into the three tiles.
+template <int LDIM, int NX>
+__device__ __forceinline__ void write_fluxes(const TileFrame<LDIM, NX>& t, const double (&g)[3][3], double jacmi,
+                                             const double (&G)[LDIM]) {
+#pragma clang fp contract(off)
+    double* tiles[3] = {t.X, t.Y, t.Z};
+#pragma unroll
+    for (int a = 0; a < LDIM; ++a) {
+        double F = g[0][a] * jacmi * G[0];
+#pragma unroll
+        for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
+        tiles[a][t.tid] = F;
+    }
+}
+
+// The fluxes of the field staged in T into the three tiles, kb = -kappa bm1.
+//   forward:  G_d = kb d_d u;  returns the advection sum_d Ub_d d_d u
+//   adjoint:  G_d = kb d_d u - bm1 Ub_d u;  returns 0
+template <bool ADJ, int LDIM, int NX>
+__device__ __forceinline__ double field_fluxes(const TileFrame<LDIM, NX>& t, const double* T, const double (&g)[3][3],
+                                               double jacmi, double bm, double kb, const double (&Ub)[LDIM]) {
+#pragma clang fp contract(off)
+    double du[LDIM], G[LDIM], adv = 0.0;
+    physical_gradient<LDIM, NX>(t.q, T, g, jacmi, du);
+#pragma unroll
+    for (int d = 0; d < LDIM; ++d) {
+        if constexpr (ADJ) {
+            G[d] = kb * du[d] - bm * Ub[d] * T[t.tid];
+        } else {
+            G[d] = kb * du[d];
+            adv = adv + Ub[d] * du[d];
+        }
+    }
+    write_fluxes(t, g, jacmi, G);
+    return adv;
+}
+
+// One base field of the adjoint pre-sweep, staged in T:  P_d <- [not first] P_d + u_f d_d B_f.
+template <int LDIM, int NX>
+__device__ __forceinline__ void presweep_field(const TilePoint<LDIM, NX>& q, const double* T, const double (&g)[3][3],
+                                               double jacmi, double uf, bool first, double (&P)[LDIM]) {
+#pragma clang fp contract(off)
+    double db[LDIM];
+    physical_gradient<LDIM, NX>(q, T, g, jacmi, db);
+#pragma unroll
+    for (int d = 0; d < LDIM; ++d) P[d] = first ? uf * db[d] : P[d] + uf * db[d];
+}
 
 // ------------------------------------------------------------------------------------------
 // The fused right-hand side: the tile of k_gradm1 (whole elements per workgroup, one point per thread).
@@ -59,84 +156,25 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_advdiff_rhs(
     int64_t u_stride, double* __restrict__ r, int64_t r_stride) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
-    const int nt = epb * pts;
-    double* D = lds;                         // D(i, m) at D[i*NX + m]
-    double* X = D + NX * NX;                 // coordinates, then the flux along r
-    double* Y = X + nt;                      // ... along s
-    double* Z = Y + nt;                      // ... along t (3-D only)
-    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const PointIndex<LDIM, NX> ix(tid);
-    const double wt = ix.weight(wg);
-    const int le = tid / pts;
-    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = D + ix.j;
-    const double* Dck = D + ix.k;
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);   // one field tile: U, the field being differentiated
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
-        double g[3][3], jac;   // dead lanes compute garbage they never store
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        int64_t p;
+        double g[3][3], jac;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
         const double jacmi = 1.0 / jac;
-        const double bm = jac * wt;
+        const double bm = jac * t.wt;
         double Ub[LDIM];
 #pragma unroll
         for (int d = 0; d < LDIM; ++d) Ub[d] = live ? ub[d * b_stride + p] : 0.0;
         for (int f = 0; f < nfld; ++f) {
             if (f > 0) __syncthreads();   // every lane is done reading the previous field and its fluxes
-            if (live) U[tid] = u[f * u_stride + p];
+            if (live) t.U[t.tid] = u[f * u_stride + p];
             __syncthreads();              // (and every lane has formed its factors: the tiles are free)
             double adv = 0.0;
-            if (live) {
-                double ur, us, ut;
-                line_sums<LDIM, NX>(q, U, ur, us, ut);
-                const double kb = -kappa[f] * bm;
-                double G[LDIM];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
-                    if constexpr (ADJ) {
-                        G[d] = kb * du - bm * Ub[d] * U[tid];
-                    } else {
-                        G[d] = kb * du;
-                        adv = adv + Ub[d] * du;
-                    }
-                }
-                double* tiles[3] = {X, Y, Z};
-#pragma unroll
-                for (int a = 0; a < LDIM; ++a) {
-                    double F = g[0][a] * jacmi * G[0];
-#pragma unroll
-                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
-                    tiles[a][tid] = F;
-                }
-            }
+            if (live) adv = field_fluxes<ADJ>(t, t.U, g, jacmi, bm, -kappa[f] * bm, Ub);
             __syncthreads();
             if (live) {
-                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-                for (int m = 1; m < NX; ++m) {
-                    tr = tr + Dci[m * NX] * X[q.ri + m];
-                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-                }
-                double acc = tr + ts;
-                if constexpr (LDIM == 3) {
-                    double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-                    acc = acc + tt;
-                }
+                const double acc = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z);
                 r[f * r_stride + p] = ADJ ? acc : acc - bm * adv;
             }
         }
@@ -150,30 +188,12 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_advdiff_bm1(
     const double* __restrict__ ym, const double* __restrict__ zm, double* __restrict__ bm1) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int nt = epb * pts;
-    double* D = lds;
-    double* X = D + NX * NX;
-    double* Y = X + nt;
-    double* Z = Y + nt;
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const double wt = PointIndex<LDIM, NX>(tid).weight(wg);
-    const int le = tid / pts;
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);   // no field tile
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
+        int64_t p;
         double g[3][3], jac;
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
-        if (live) bm1[p] = jac * wt;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
+        if (live) bm1[p] = jac * t.wt;
     }
 }
 
@@ -318,38 +338,15 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_linconv_rhs(
     int64_t u_stride, double* __restrict__ r, int64_t r_stride) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
-    const int nt = epb * pts;
-    double* D = lds;                         // D(i, m) at D[i*NX + m]
-    double* X = D + NX * NX;                 // coordinates, then the flux along r
-    double* Y = X + nt;                      // ... along s
-    double* Z = Y + nt;                      // ... along t (3-D only)
-    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated
-    double* Bt = U + nt;                     // the base field being differentiated
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const PointIndex<LDIM, NX> ix(tid);
-    const double wt = ix.weight(wg);
-    const int le = tid / pts;
-    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = D + ix.j;
-    const double* Dck = D + ix.k;
+    // two field tiles: U, the field being differentiated, and Bt, the base field being differentiated
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);
+    const int tid = t.tid;
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
-        double g[3][3], jac;   // dead lanes compute garbage they never store
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        int64_t p;
+        double g[3][3], jac;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
         const double jacmi = 1.0 / jac;
-        const double bm = jac * wt;
+        const double bm = jac * t.wt;
         double Ub[LDIM];       // the advecting velocity B_d
         double P[LDIM];        // forward: the velocity perturbation u_d; adjoint: sum_f' u_f' d_d B_f'
 #pragma unroll
@@ -359,80 +356,37 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_linconv_rhs(
         }
         if constexpr (ADJ) {
             for (int f = 0; f < nfld; ++f) {
-                double* T = (f & 1) ? Bt : U;   // the tile written two fields ago: a barrier lies between
+                double* T = (f & 1) ? t.Bt : t.U;   // the tile written two fields ago: a barrier lies between
                 if (live) T[tid] = B[f * b_stride + p];
                 __syncthreads();
-                if (live) {
-                    double br, bs, bt;
-                    line_sums<LDIM, NX>(q, T, br, bs, bt);
-                    const double uf = u[f * u_stride + p];
-#pragma unroll
-                    for (int d = 0; d < LDIM; ++d) {
-                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
-                        P[d] = f == 0 ? uf * db : P[d] + uf * db;
-                    }
-                }
+                if (live) presweep_field<LDIM, NX>(t.q, T, g, jacmi, u[f * u_stride + p], f == 0, P);
             }
         }
         for (int f = 0; f < nfld; ++f) {
             if (f > 0 || ADJ) __syncthreads();   // every lane is done reading the previous field and its fluxes
             if (live) {
-                U[tid] = u[f * u_stride + p];
-                if constexpr (!ADJ) Bt[tid] = B[f * b_stride + p];
+                t.U[tid] = u[f * u_stride + p];
+                if constexpr (!ADJ) t.Bt[tid] = B[f * b_stride + p];
             }
             __syncthreads();              // (and every lane has formed its factors: the tiles are free)
             double adv = 0.0, prod = 0.0;
             if (live) {
-                double ur, us, ut;
-                line_sums<LDIM, NX>(q, U, ur, us, ut);
-                const double kb = -kappa[f] * bm;
-                double G[LDIM];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
-                    if constexpr (ADJ) {
-                        G[d] = kb * du - bm * Ub[d] * U[tid];
-                    } else {
-                        G[d] = kb * du;
-                        adv = adv + Ub[d] * du;
-                    }
-                }
                 if constexpr (!ADJ) {
-                    double br, bs, bt;
-                    line_sums<LDIM, NX>(q, Bt, br, bs, bt);
-                    prod = P[0] * physical_derivative<LDIM>(g, jacmi, 0, br, bs, bt);
+                    double db[LDIM];
+                    physical_gradient<LDIM, NX>(t.q, t.Bt, g, jacmi, db);
+                    prod = P[0] * db[0];
 #pragma unroll
-                    for (int d = 1; d < LDIM; ++d)
-                        prod = prod + P[d] * physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
+                    for (int d = 1; d < LDIM; ++d) prod = prod + P[d] * db[d];
                 } else {
 #pragma unroll
                     for (int d = 0; d < LDIM; ++d)
                         if (f == d) prod = P[d];
                 }
-                double* tiles[3] = {X, Y, Z};
-#pragma unroll
-                for (int a = 0; a < LDIM; ++a) {
-                    double F = g[0][a] * jacmi * G[0];
-#pragma unroll
-                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
-                    tiles[a][tid] = F;
-                }
+                adv = field_fluxes<ADJ>(t, t.U, g, jacmi, bm, -kappa[f] * bm, Ub);
             }
             __syncthreads();
             if (live) {
-                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-                for (int m = 1; m < NX; ++m) {
-                    tr = tr + Dci[m * NX] * X[q.ri + m];
-                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-                }
-                double acc = tr + ts;
-                if constexpr (LDIM == 3) {
-                    double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-                    acc = acc + tt;
-                }
+                const double acc = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z);
                 if constexpr (ADJ)
                     r[f * r_stride + p] = f < LDIM ? acc - bm * prod : acc;
                 else
@@ -534,55 +488,16 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>()), 4) void k_burgers_tange
     int64_t u_stride, double* __restrict__ rB, int64_t rb_stride, double* __restrict__ ru, int64_t ru_stride) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
-    const int nt = epb * pts;
-    double* D = lds;                         // D(i, m) at D[i*NX + m]
-    double* X = D + NX * NX;                 // coordinates, then the flux along r (of B, then of u)
-    double* Y = X + nt;                      // ... along s
-    double* Z = Y + nt;                      // ... along t (3-D only)
-    double* U = LDIM == 3 ? Z + nt : Z;      // the perturbation field being differentiated
-    double* Bt = U + nt;                     // the base field being differentiated
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const PointIndex<LDIM, NX> ix(tid);
-    const double wt = ix.weight(wg);
-    const int le = tid / pts;
-    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = D + ix.j;
-    const double* Dck = D + ix.k;
-    // sum_a D_a^T of the fluxes in the three tiles
-    auto transposed_sums = [&]() {
-        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-        for (int m = 1; m < NX; ++m) {
-            tr = tr + Dci[m * NX] * X[q.ri + m];
-            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-        }
-        double acc = tr + ts;
-        if constexpr (LDIM == 3) {
-            double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-            acc = acc + tt;
-        }
-        return acc;
-    };
+    // two field tiles: U, the perturbation field being differentiated, and Bt, the base field; the flux tiles
+    // hold the fluxes of B, then of u
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);
+    const int tid = t.tid;
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
-        double g[3][3], jac;   // dead lanes compute garbage they never store
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        int64_t p;
+        double g[3][3], jac;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
         const double jacmi = 1.0 / jac;
-        const double bm = jac * wt;
+        const double bm = jac * t.wt;
         double Ub[LDIM];       // the advecting velocity B_d
         double P[LDIM];        // the velocity perturbation u_d
 #pragma unroll
@@ -590,43 +505,34 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>()), 4) void k_burgers_tange
             Ub[d] = live ? B[d * b_stride + p] : 0.0;
             P[d] = live ? u[d * u_stride + p] : 0.0;
         }
-        double* tiles[3] = {X, Y, Z};
         for (int f = 0; f < nfld; ++f) {
             // (every lane differentiated the previous field before that field's last barrier)
             if (live) {
-                U[tid] = u[f * u_stride + p];
-                Bt[tid] = B[f * b_stride + p];
+                t.U[tid] = u[f * u_stride + p];
+                t.Bt[tid] = B[f * b_stride + p];
             }
             __syncthreads();   // (and every lane has formed its factors / read the previous fluxes of u)
             double advB = 0.0, advu = 0.0, prod = 0.0;
             const double kb = live ? -kappa[f] * bm : 0.0;
-            // the fluxes F_a of one staged field into the three tiles; its advection by B_vel is returned
-            auto fluxes = [&](const double* T, double& adv, bool production) {
-                double tr, ts, tt;
-                line_sums<LDIM, NX>(q, T, tr, ts, tt);
-                double G[LDIM];
+            if (live) {
+                // field_fluxes of B_f, spelled out: the production term rides on the derivatives of the base state
+                double dB[LDIM], G[LDIM];
+                physical_gradient<LDIM, NX>(t.q, t.Bt, g, jacmi, dB);
 #pragma unroll
                 for (int d = 0; d < LDIM; ++d) {
-                    const double dd = physical_derivative<LDIM>(g, jacmi, d, tr, ts, tt);
-                    G[d] = kb * dd;
-                    adv = adv + Ub[d] * dd;
-                    if (production) prod = d == 0 ? P[0] * dd : prod + P[d] * dd;
+                    G[d] = kb * dB[d];
+                    advB = advB + Ub[d] * dB[d];
+                    prod = d == 0 ? P[0] * dB[d] : prod + P[d] * dB[d];
                 }
-#pragma unroll
-                for (int a = 0; a < LDIM; ++a) {
-                    double F = g[0][a] * jacmi * G[0];
-#pragma unroll
-                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
-                    tiles[a][tid] = F;
-                }
-            };
-            if (live) fluxes(Bt, advB, true);
+                write_fluxes(t, g, jacmi, G);
+            }
             __syncthreads();
-            if (live) rB[f * rb_stride + p] = transposed_sums() - bm * advB;
+            if (live) rB[f * rb_stride + p] = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z) - bm * advB;
             __syncthreads();   // the fluxes of B are read
-            if (live) fluxes(U, advu, false);
+            if (live) advu = field_fluxes<false>(t, t.U, g, jacmi, bm, kb, Ub);
             __syncthreads();
-            if (live) ru[f * ru_stride + p] = (transposed_sums() - bm * advu) - bm * prod;
+            if (live)
+                ru[f * ru_stride + p] = (transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z) - bm * advu) - bm * prod;
         }
     }
 }
@@ -762,55 +668,16 @@ __global__ NKV_CRHS_BOUNDS((tile_threads<LDIM, NX>())) void k_linconv_crhs(
     int64_t r_stride) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
-    const int nt = epb * pts;
-    double* D = lds;                         // D(i, m) at D[i*NX + m]
-    double* X = D + NX * NX;                 // coordinates, then the flux along r (of the re, then of the im half)
-    double* Y = X + nt;                      // ... along s
-    double* Z = Y + nt;                      // ... along t (3-D only)
-    double* U = LDIM == 3 ? Z + nt : Z;      // the field being differentiated (re, then im)
-    double* Bt = U + nt;                     // the base field being differentiated
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const PointIndex<LDIM, NX> ix(tid);
-    const double wt = ix.weight(wg);
-    const int le = tid / pts;
-    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = D + ix.j;
-    const double* Dck = D + ix.k;
-    // sum_a D_a^T of the fluxes in the three tiles
-    auto transposed_sums = [&]() {
-        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-        for (int m = 1; m < NX; ++m) {
-            tr = tr + Dci[m * NX] * X[q.ri + m];
-            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-        }
-        double acc = tr + ts;
-        if constexpr (LDIM == 3) {
-            double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-            acc = acc + tt;
-        }
-        return acc;
-    };
+    // two field tiles: U, the field being differentiated (re, then im), and Bt, the base field being
+    // differentiated; the flux tiles hold the fluxes of the re, then of the im half
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);
+    const int tid = t.tid;
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
-        double g[3][3], jac;   // dead lanes compute garbage they never store
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        int64_t p;
+        double g[3][3], jac;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
         const double jacmi = 1.0 / jac;
-        const double bm = jac * wt;
+        const double bm = jac * t.wt;
         double Ub[LDIM];       // the advecting velocity B_d
         double Pr[LDIM];       // forward: the velocity perturbation u_re,d; adjoint: sum_f' u_re,f' d_d B_f'
         double Pi[LDIM];       // ... of the im half
@@ -822,67 +689,41 @@ __global__ NKV_CRHS_BOUNDS((tile_threads<LDIM, NX>())) void k_linconv_crhs(
         }
         if constexpr (ADJ) {
             for (int f = 0; f < nfld; ++f) {
-                double* T = (f & 1) ? Bt : U;   // the tile written two fields ago: a barrier lies between
+                double* T = (f & 1) ? t.Bt : t.U;   // the tile written two fields ago: a barrier lies between
                 if (live) T[tid] = B[f * b_stride + p];
                 __syncthreads();
                 if (live) {
-                    double br, bs, bt;
-                    line_sums<LDIM, NX>(q, T, br, bs, bt);
+                    // presweep_field spelled out: one differentiation of B_f' serves both halves
+                    double db[LDIM];
+                    physical_gradient<LDIM, NX>(t.q, T, g, jacmi, db);
                     const double ur = u_re[f * u_stride + p], ui = u_im[f * u_stride + p];
 #pragma unroll
                     for (int d = 0; d < LDIM; ++d) {
-                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
-                        Pr[d] = f == 0 ? ur * db : Pr[d] + ur * db;
-                        Pi[d] = f == 0 ? ui * db : Pi[d] + ui * db;
+                        Pr[d] = f == 0 ? ur * db[d] : Pr[d] + ur * db[d];
+                        Pi[d] = f == 0 ? ui * db[d] : Pi[d] + ui * db[d];
                     }
                 }
             }
             __syncthreads();   // every lane is done reading the last base field
         }
-        double* tiles[3] = {X, Y, Z};
         for (int f = 0; f < nfld; ++f) {
             // (every lane differentiated the previous field before that field's last barrier)
             if (live) {
-                U[tid] = u_re[f * u_stride + p];
-                if constexpr (!ADJ) Bt[tid] = B[f * b_stride + p];
+                t.U[tid] = u_re[f * u_stride + p];
+                if constexpr (!ADJ) t.Bt[tid] = B[f * b_stride + p];
             }
             __syncthreads();   // (and every lane has formed its factors / read the previous fluxes)
             const double kb = live ? -kappa[f] * bm : 0.0;
             double prod_re = 0.0, prod_im = 0.0;
-            // the fluxes F_a of the staged half into the three tiles; forward: its advection by B_vel is returned
-            auto fluxes = [&]() {
-                double ur, us, ut, adv = 0.0;
-                line_sums<LDIM, NX>(q, U, ur, us, ut);
-                double G[LDIM];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
-                    if constexpr (ADJ) {
-                        G[d] = kb * du - bm * Ub[d] * U[tid];
-                    } else {
-                        G[d] = kb * du;
-                        adv = adv + Ub[d] * du;
-                    }
-                }
-#pragma unroll
-                for (int a = 0; a < LDIM; ++a) {
-                    double F = g[0][a] * jacmi * G[0];
-#pragma unroll
-                    for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
-                    tiles[a][tid] = F;
-                }
-                return adv;
-            };
             double adv = 0.0;
             if (live) {
                 if constexpr (!ADJ) {
-                    double br, bs, bt;
-                    line_sums<LDIM, NX>(q, Bt, br, bs, bt);
+                    double db[LDIM];
+                    physical_gradient<LDIM, NX>(t.q, t.Bt, g, jacmi, db);
 #pragma unroll
                     for (int d = 0; d < LDIM; ++d) {
-                        const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
-                        prod_re = d == 0 ? Pr[0] * db : prod_re + Pr[d] * db;
-                        prod_im = d == 0 ? Pi[0] * db : prod_im + Pi[d] * db;
+                        prod_re = d == 0 ? Pr[0] * db[d] : prod_re + Pr[d] * db[d];
+                        prod_im = d == 0 ? Pi[0] * db[d] : prod_im + Pi[d] * db[d];
                     }
                 } else {
 #pragma unroll
@@ -892,22 +733,22 @@ __global__ NKV_CRHS_BOUNDS((tile_threads<LDIM, NX>())) void k_linconv_crhs(
                             prod_im = Pi[d];
                         }
                 }
-                adv = fluxes();
+                adv = field_fluxes<ADJ>(t, t.U, g, jacmi, bm, kb, Ub);
             }
             __syncthreads();
             if (live) {
-                const double acc = transposed_sums();
+                const double acc = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z);
                 if constexpr (ADJ)
                     r_re[f * r_stride + p] = f < LDIM ? acc - bm * prod_re : acc;
                 else
                     r_re[f * r_stride + p] = (acc - bm * adv) - bm * prod_re;
-                U[tid] = u_im[f * u_stride + p];   // the re half was differentiated before the barrier above
+                t.U[tid] = u_im[f * u_stride + p];   // the re half was differentiated before the barrier above
             }
             __syncthreads();   // the fluxes of the re half are read, the im half is staged
-            if (live) adv = fluxes();
+            if (live) adv = field_fluxes<ADJ>(t, t.U, g, jacmi, bm, kb, Ub);
             __syncthreads();
             if (live) {
-                const double acc = transposed_sums();
+                const double acc = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z);
                 if constexpr (ADJ)
                     r_im[f * r_stride + p] = f < LDIM ? acc - bm * prod_im : acc;
                 else
@@ -955,91 +796,29 @@ __global__ NKV_BWD_BOUNDS((tile_threads<LDIM, NX>())) void k_burgers_backward_rh
     int64_t rx_stride, double* __restrict__ ru, int64_t ru_stride) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
-    constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
-    const int nt = epb * pts;
-    double* D = lds;                         // D(i, m) at D[i*NX + m]
-    double* X = D + NX * NX;                 // coordinates, then the flux along r (of X, then of u)
-    double* Y = X + nt;                      // ... along s
-    double* Z = Y + nt;                      // ... along t (3-D only)
-    double* U = LDIM == 3 ? Z + nt : Z;      // the two field tiles: staged fields alternate between them
-    double* Bt = U + nt;
-    const int tid = threadIdx.x;
-    for (int t = tid; t < NX * NX; t += blockDim.x) D[t] = Dg[t];
-    const TilePoint<LDIM, NX> q(D, tid, nt);
-    const PointIndex<LDIM, NX> ix(tid);
-    const double wt = ix.weight(wg);
-    const int le = tid / pts;
-    const double* Dci = D + ix.i;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = D + ix.j;
-    const double* Dck = D + ix.k;
-    // sum_a D_a^T of the fluxes in the three tiles
-    auto transposed_sums = [&]() {
-        double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-        for (int m = 1; m < NX; ++m) {
-            tr = tr + Dci[m * NX] * X[q.ri + m];
-            ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-        }
-        double acc = tr + ts;
-        if constexpr (LDIM == 3) {
-            double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-            for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-            acc = acc + tt;
-        }
-        return acc;
-    };
+    // two field tiles, U and Bt: staged fields alternate between them; the flux tiles hold the fluxes of X,
+    // then of u
+    const TileFrame<LDIM, NX> t(lds, epb, Dg, wg);
+    const int tid = t.tid;
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
-        const int64_t p = e0 * pts + tid;
-        const bool live = tid < nt && e0 + le < nel;
-        __syncthreads();   // the previous group's reads are done (and D is staged on the first pass)
-        if (live) {
-            X[tid] = xm[p];
-            Y[tid] = ym[p];
-            if (LDIM == 3) Z[tid] = zm[p];
-        }
-        __syncthreads();
-        double g[3][3], jac;   // dead lanes compute garbage they never store
-        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        int64_t p;
+        double g[3][3], jac;
+        const bool live = t.begin_group(e0, nel, xm, ym, zm, p, g, jac);
         const double jacmi = 1.0 / jac;
-        const double bm = jac * wt;
-        double* tiles[3] = {X, Y, Z};
-        // G_d -> the fluxes F_a into the three tiles
-        auto write_fluxes = [&](const double (&G)[LDIM]) {
-#pragma unroll
-            for (int a = 0; a < LDIM; ++a) {
-                double F = g[0][a] * jacmi * G[0];
-#pragma unroll
-                for (int d = 1; d < LDIM; ++d) F = F + g[d][a] * jacmi * G[d];
-                tiles[a][tid] = F;
-            }
-        };
+        const double bm = jac * t.wt;
         int stage = 0;         // fields staged so far in this group: the next one goes to tile (stage & 1)
         double Ub[LDIM];       // the advecting velocity: X_d, then S_d
         // ---- the X sweep: k_advdiff_rhs<.., false> with u = U = X ----
 #pragma unroll
         for (int d = 0; d < LDIM; ++d) Ub[d] = live ? Xs[d * x_stride + p] : 0.0;
         for (int f = 0; f < nfld; ++f, ++stage) {
-            double* T = (stage & 1) ? Bt : U;   // last read two fields ago: a barrier lies between
+            double* T = (stage & 1) ? t.Bt : t.U;   // last read two fields ago: a barrier lies between
             if (live) T[tid] = Xs[f * x_stride + p];
             __syncthreads();   // (every lane has formed its factors / read the previous field's fluxes)
             double adv = 0.0;
-            if (live) {
-                double ur, us, ut;
-                line_sums<LDIM, NX>(q, T, ur, us, ut);
-                const double kb = -kappa[f] * bm;
-                double G[LDIM];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
-                    G[d] = kb * du;
-                    adv = adv + Ub[d] * du;
-                }
-                write_fluxes(G);
-            }
+            if (live) adv = field_fluxes<false>(t, T, g, jacmi, bm, -kappa[f] * bm, Ub);
             __syncthreads();
-            if (live) rX[f * rx_stride + p] = transposed_sums() - bm * adv;
+            if (live) rX[f * rx_stride + p] = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z) - bm * adv;
         }
         // ---- the adjoint: k_linconv_rhs<.., true> of u about S ----
         double P[LDIM];        // sum_f' u_f' d_d S_f'
@@ -1049,141 +828,85 @@ __global__ NKV_BWD_BOUNDS((tile_threads<LDIM, NX>())) void k_burgers_backward_rh
             P[d] = 0.0;
         }
         for (int f = 0; f < nfld; ++f, ++stage) {
-            double* T = (stage & 1) ? Bt : U;
+            double* T = (stage & 1) ? t.Bt : t.U;
             if (live) T[tid] = Sb[f * s_stride + p];
             __syncthreads();
-            if (live) {
-                double br, bs, bt;
-                line_sums<LDIM, NX>(q, T, br, bs, bt);
-                const double uf = u[f * u_stride + p];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double db = physical_derivative<LDIM>(g, jacmi, d, br, bs, bt);
-                    P[d] = f == 0 ? uf * db : P[d] + uf * db;
-                }
-            }
+            if (live) presweep_field<LDIM, NX>(t.q, T, g, jacmi, u[f * u_stride + p], f == 0, P);
         }
         for (int f = 0; f < nfld; ++f, ++stage) {
-            double* T = (stage & 1) ? Bt : U;
+            double* T = (stage & 1) ? t.Bt : t.U;
             if (live) T[tid] = u[f * u_stride + p];
             __syncthreads();   // (every lane has read the fluxes of the field before: of X the first time)
             double prod = 0.0;
             if (live) {
-                double ur, us, ut;
-                line_sums<LDIM, NX>(q, T, ur, us, ut);
-                const double kb = -kappa[f] * bm;
-                double G[LDIM];
-#pragma unroll
-                for (int d = 0; d < LDIM; ++d) {
-                    const double du = physical_derivative<LDIM>(g, jacmi, d, ur, us, ut);
-                    G[d] = kb * du - bm * Ub[d] * T[tid];
-                }
+                field_fluxes<true>(t, T, g, jacmi, bm, -kappa[f] * bm, Ub);
 #pragma unroll
                 for (int d = 0; d < LDIM; ++d)
                     if (f == d) prod = P[d];
-                write_fluxes(G);
             }
             __syncthreads();
             if (live) {
-                const double acc = transposed_sums();
+                const double acc = transposed_line_sums<LDIM, NX>(t.q, t.X, t.Y, t.Z);
                 ru[f * ru_stride + p] = f < LDIM ? acc - bm * prod : acc;
             }
         }
     }
 }
 
-template <int LDIM, int NX>
-void launch_rhs(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
-                const double* zm, const double* ub, int64_t b_stride, const double* kappa, const double* u,
-                int64_t u_stride, double* r, int64_t r_stride, int adjoint, hipStream_t st) {
+// ------------------------------------------------------------------------------------------
+// The host side the tiled entries share.
+// ------------------------------------------------------------------------------------------
+
+// The launcher of every tiled kernel: NF field tiles behind the LDIM coordinate tiles size the dynamic LDS
+// (lx1^2 + (LDIM + NF) nt doubles, below 64 KiB: no attribute to raise); args follow (nel, epb).
+template <int LDIM, int NX, int NF, typename Kernel, typename... Args>
+void launch_tiled(Kernel kernel, int64_t nel, hipStream_t st, Args... args) {
     constexpr int pts = tile_pts<LDIM, NX>();
     const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 1) * epb * pts);
+    static_assert(NF >= 0 && NF <= 2, "a tiled kernel has at most two field tiles");
+    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + NF) * epb * pts);
     static_assert(sizeof(double) * (10 * 10 + 4 * 1000) <= 65536, "dynamic LDS within 64 KiB at lx1 = 10");
-    const int64_t groups = (nel + epb - 1) / epb;
-    const int grid = (int)std::min<int64_t>(groups, 16384);
-    if (adjoint)
-        hipLaunchKernelGGL((k_advdiff_rhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
-                           nfld, D, w, xm, ym, zm, ub, b_stride, kappa, u, u_stride, r, r_stride);
-    else
-        hipLaunchKernelGGL((k_advdiff_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
-                           epb, nfld, D, w, xm, ym, zm, ub, b_stride, kappa, u, u_stride, r, r_stride);
-}
-
-template <int LDIM, int NX>
-void launch_bm1(int64_t nel, const double* D, const double* w, const double* xm, const double* ym, const double* zm,
-                double* bm1, hipStream_t st) {
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)LDIM * epb * pts);
-    const int64_t groups = (nel + epb - 1) / epb;
-    const int grid = (int)std::min<int64_t>(groups, 16384);
-    hipLaunchKernelGGL((k_advdiff_bm1<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, w, xm,
-                       ym, zm, bm1);
-}
-
-template <int LDIM, int NX>
-void launch_linconv(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
-                    const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u,
-                    int64_t u_stride, double* r, int64_t r_stride, int adjoint, hipStream_t st) {
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);
     static_assert(sizeof(double) * (10 * 10 + 5 * 1000) <= 65536, "dynamic LDS within 64 KiB at lx1 = 10");
     const int64_t groups = (nel + epb - 1) / epb;
     const int grid = (int)std::min<int64_t>(groups, 16384);
-    if (adjoint)
-        hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
-                           nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
-    else
-        hipLaunchKernelGGL((k_linconv_rhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
-                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, r, r_stride);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, args...);
 }
 
-template <int LDIM, int NX>
-void launch_linconv_pair(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
-                         const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u_re,
-                         const double* u_im, int64_t u_stride, double* r_re, double* r_im, int64_t r_stride,
-                         int adjoint, hipStream_t st) {
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
-    const int64_t groups = (nel + epb - 1) / epb;
-    const int grid = (int)std::min<int64_t>(groups, 16384);
-    if (adjoint)
-        hipLaunchKernelGGL((k_linconv_crhs<LDIM, NX, true>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
-                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u_re, u_im, u_stride, r_re, r_im, r_stride);
-    else
-        hipLaunchKernelGGL((k_linconv_crhs<LDIM, NX, false>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel,
-                           epb, nfld, D, w, xm, ym, zm, B, b_stride, kappa, u_re, u_im, u_stride, r_re, r_im, r_stride);
+// The lx1 x ldim dispatch: calls f(ldim, lx1) with both as integral constants.  check_mesh_args has let
+// through ldim = 2, 3 and lx1 = 2..10 only.
+template <typename F>
+void dispatch_tile(int lx1, int ldim, F&& f) {
+#define NKV_AD_CASE(NX)                                                                          \
+    case NX:                                                                                     \
+        if (ldim == 3) f(std::integral_constant<int, 3>{}, std::integral_constant<int, NX>{});   \
+        else f(std::integral_constant<int, 2>{}, std::integral_constant<int, NX>{});             \
+        break;
+    switch (lx1) { NKV_PP_CASES(NKV_AD_CASE) }
+#undef NKV_AD_CASE
 }
 
-template <int LDIM, int NX>
-void launch_tangent(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
-                    const double* zm, const double* B, int64_t b_stride, const double* kappa, const double* u,
-                    int64_t u_stride, double* rB, int64_t rb_stride, double* ru, int64_t ru_stride, hipStream_t st) {
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
-    const int64_t groups = (nel + epb - 1) / epb;
-    const int grid = (int)std::min<int64_t>(groups, 16384);
-    hipLaunchKernelGGL((k_burgers_tangent_rhs<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
-                       nfld, D, w, xm, ym, zm, B, b_stride, kappa, u, u_stride, rB, rb_stride, ru, ru_stride);
+// Whether the spans of two operands of nfld fields (n points each, a stride apart) meet.
+inline bool spans_meet(const double* p, int64_t ps, const double* o, int64_t os, int nfld, int64_t n) {
+    const double* pe = p + (int64_t)(nfld - 1) * ps + n;
+    const double* oe = o + (int64_t)(nfld - 1) * os + n;
+    return p < oe && o < pe;
 }
 
-template <int LDIM, int NX>
-void launch_backward(int64_t nel, int nfld, const double* D, const double* w, const double* xm, const double* ym,
-                     const double* zm, const double* X, int64_t x_stride, const double* Sb, int64_t s_stride,
-                     const double* kappa, const double* u, int64_t u_stride, double* rX, int64_t rx_stride, double* ru,
-                     int64_t ru_stride, hipStream_t st) {
-    constexpr int pts = tile_pts<LDIM, NX>();
-    const int epb = tile_epb(pts);
-    const size_t lds = sizeof(double) * ((size_t)NX * NX + (size_t)(LDIM + 2) * epb * pts);   // k_linconv_rhs's
-    const int64_t groups = (nel + epb - 1) / epb;
-    const int grid = (int)std::min<int64_t>(groups, 16384);
-    hipLaunchKernelGGL((k_burgers_backward_rhs<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb,
-                       nfld, D, w, xm, ym, zm, X, x_stride, Sb, s_stride, kappa, u, u_stride, rX, rx_stride, ru,
-                       ru_stride);
+// What every tiled entry checks first: the layout, the mesh arguments and the four arrays all of them read.
+// *nel: the elements of this shard; 0 for an empty shard (more ranks than elements), which has nothing to
+// touch and whose pointers are not looked at: the entry returns NKV_OK.
+inline int check_tiled_entry(const char* who, const nkv_layout* L, int lx1, int ldim, const double* D, const double* w,
+                             const double* xm, const double* ym, const double* zm, int64_t* nel) {
+    *nel = 0;
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;
+    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    CHECK(need(D, who, "D"));
+    CHECK(need(w, who, "w"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    *nel = L->n_v / (ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1);
+    return NKV_OK;
 }
 
 }  // namespace
@@ -1195,36 +918,24 @@ int nkv_advdiff_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, con
                     const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
                     void* stream) {
     static const char who[] = "advdiff_rhs";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     if (nfld < 1) return fail(NKV_EINVAL, "%s: nfld=%d < 1", who, nfld);
     if (U_stride < L->n_v || u_stride < L->n_v || r_stride < L->n_v)
         return fail(NKV_EINVAL, "%s: strides U_stride=%lld u_stride=%lld r_stride=%lld below n_v=%lld", who,
                     (long long)U_stride, (long long)u_stride, (long long)r_stride, (long long)L->n_v);
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
     CHECK(need(U, who, "U"));
     CHECK(need(kappa, who, "kappa"));
     CHECK(need(u, who, "u"));
     CHECK(need(r, who, "r"));
     if (u == r) return fail(NKV_EINVAL, "%s cannot run in place (r is u)", who);
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_AD_RHS(NX)                                                                                            \
-    case NX:                                                                                                      \
-        if (ldim == 3)                                                                                            \
-            launch_rhs<3, NX>(nel, nfld, D, w, xm, ym, zm, U, U_stride, kappa, u, u_stride, r, r_stride, adjoint, \
-                              st);                                                                                \
-        else                                                                                                      \
-            launch_rhs<2, NX>(nel, nfld, D, w, xm, ym, zm, U, U_stride, kappa, u, u_stride, r, r_stride, adjoint, \
-                              st);                                                                                \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_AD_RHS) }
-#undef NKV_AD_RHS
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        auto kernel = adjoint ? k_advdiff_rhs<LD, NX, true> : k_advdiff_rhs<LD, NX, false>;
+        launch_tiled<LD, NX, 1>(kernel, nel, S(stream), nfld, D, w, xm, ym, zm, U, U_stride, kappa, u, u_stride, r,
+                                r_stride);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -1232,24 +943,14 @@ int nkv_advdiff_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, con
 int nkv_advdiff_bm1(const nkv_layout* L, int lx1, int ldim, const double* D, const double* w, const double* xm,
                     const double* ym, const double* zm, double* bm1, void* stream) {
     static const char who[] = "advdiff_bm1";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     CHECK(need(bm1, who, "bm1"));
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_AD_BM1(NX)                                                          \
-    case NX:                                                                    \
-        if (ldim == 3) launch_bm1<3, NX>(nel, D, w, xm, ym, zm, bm1, st);       \
-        else launch_bm1<2, NX>(nel, D, w, xm, ym, zm, bm1, st);                 \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_AD_BM1) }
-#undef NKV_AD_BM1
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        launch_tiled<LD, NX, 0>(k_advdiff_bm1<LD, NX>, nel, S(stream), D, w, xm, ym, zm, bm1);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -1358,43 +1059,30 @@ int nkv_linconv_rhs(const nkv_layout* L, int lx1, int ldim, const double* D, con
                     const double* u, int nfld, int64_t u_stride, double* r, int64_t r_stride, int adjoint,
                     void* stream) {
     static const char who[] = "linconv_rhs";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
                                  nfld, ldim);
     if (B_stride < L->n_v || u_stride < L->n_v || r_stride < L->n_v)
         return fail(NKV_EINVAL, "%s: strides B_stride=%lld u_stride=%lld r_stride=%lld below n_v=%lld", who,
                     (long long)B_stride, (long long)u_stride, (long long)r_stride, (long long)L->n_v);
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
     CHECK(need(B, who, "B"));
     CHECK(need(kappa, who, "kappa"));
     CHECK(need(u, who, "u"));
     CHECK(need(r, who, "r"));
     // r is written field by field while later fields of u and B are still to be read: no overlap of the spans
-    auto meets_r = [&](const double* p, int64_t stride) {
-        const double* e = p + (int64_t)(nfld - 1) * stride + L->n_v;
-        const double* re = r + (int64_t)(nfld - 1) * r_stride + L->n_v;
-        return p < re && r < e;
+    auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
+        return spans_meet(p, ps, o, os, nfld, L->n_v);
     };
-    if (meets_r(u, u_stride) || meets_r(B, B_stride)) return fail(NKV_EINVAL, "%s: r overlaps u or B", who);
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_LC_RHS(NX)                                                                                                \
-    case NX:                                                                                                          \
-        if (ldim == 3)                                                                                                \
-            launch_linconv<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r, r_stride, adjoint, \
-                                  st);                                                                                \
-        else                                                                                                          \
-            launch_linconv<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r, r_stride, adjoint, \
-                                  st);                                                                                \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_LC_RHS) }
-#undef NKV_LC_RHS
+    if (meets(u, u_stride, r, r_stride) || meets(B, B_stride, r, r_stride))
+        return fail(NKV_EINVAL, "%s: r overlaps u or B", who);
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        auto kernel = adjoint ? k_linconv_rhs<LD, NX, true> : k_linconv_rhs<LD, NX, false>;
+        launch_tiled<LD, NX, 2>(kernel, nel, S(stream), nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r,
+                                r_stride);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -1404,9 +1092,9 @@ int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, co
                      const double* u_re, const double* u_im, int nfld, int64_t u_stride, double* r_re, double* r_im,
                      int64_t r_stride, int adjoint, void* stream) {
     static const char who[] = "linconv_crhs";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
                                  nfld, ldim);
     if (B_stride < L->n_v) return fail(NKV_EINVAL, "%s: B_stride=%lld below n_v=%lld", who, (long long)B_stride,
@@ -1415,10 +1103,6 @@ int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, co
                                        (long long)L->n_v);
     if (r_stride < L->n_v) return fail(NKV_EINVAL, "%s: r_stride=%lld below n_v=%lld", who, (long long)r_stride,
                                        (long long)L->n_v);
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
     CHECK(need(B, who, "B"));
     CHECK(need(kappa, who, "kappa"));
     CHECK(need(u_re, who, "u_re"));
@@ -1430,7 +1114,7 @@ int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, co
     // where the whole spans meet the field segments decide
     auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
         const int64_t n = L->n_v;
-        if (!(p < o + (int64_t)(nfld - 1) * os + n && o < p + (int64_t)(nfld - 1) * ps + n)) return false;
+        if (!spans_meet(p, ps, o, os, nfld, n)) return false;
         for (int i = 0; i < nfld; ++i)
             for (int j = 0; j < nfld; ++j) {
                 const double *a = p + (int64_t)i * ps, *b = o + (int64_t)j * os;
@@ -1445,20 +1129,12 @@ int nkv_linconv_crhs(const nkv_layout* L, int lx1, int ldim, const double* D, co
     if (meets(u_re, u_stride, r_im, r_stride) || meets(u_im, u_stride, r_im, r_stride) ||
         meets(B, B_stride, r_im, r_stride))
         return fail(NKV_EINVAL, "%s: r_im overlaps u_re, u_im or B", who);
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_LC_CRHS(NX)                                                                                               \
-    case NX:                                                                                                          \
-        if (ldim == 3)                                                                                                \
-            launch_linconv_pair<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u_re, u_im, u_stride, r_re,   \
-                                       r_im, r_stride, adjoint, st);                                                  \
-        else                                                                                                          \
-            launch_linconv_pair<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u_re, u_im, u_stride, r_re,   \
-                                       r_im, r_stride, adjoint, st);                                                  \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_LC_CRHS) }
-#undef NKV_LC_CRHS
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        auto kernel = adjoint ? k_linconv_crhs<LD, NX, true> : k_linconv_crhs<LD, NX, false>;
+        launch_tiled<LD, NX, 2>(kernel, nel, S(stream), nfld, D, w, xm, ym, zm, B, B_stride, kappa, u_re, u_im,
+                                u_stride, r_re, r_im, r_stride);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -1525,19 +1201,15 @@ int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double
                             const double* u, int nfld, int64_t u_stride, double* r_B, int64_t rB_stride, double* r_u,
                             int64_t ru_stride, void* stream) {
     static const char who[] = "burgers_tangent_rhs";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the base state's first ldim fields advect)", who,
                                  nfld, ldim);
     if (B_stride < L->n_v || u_stride < L->n_v || rB_stride < L->n_v || ru_stride < L->n_v)
         return fail(NKV_EINVAL, "%s: strides B_stride=%lld u_stride=%lld rB_stride=%lld ru_stride=%lld below n_v=%lld",
                     who, (long long)B_stride, (long long)u_stride, (long long)rB_stride, (long long)ru_stride,
                     (long long)L->n_v);
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
     CHECK(need(B, who, "B"));
     CHECK(need(kappa, who, "kappa"));
     CHECK(need(u, who, "u"));
@@ -1545,29 +1217,18 @@ int nkv_burgers_tangent_rhs(const nkv_layout* L, int lx1, int ldim, const double
     CHECK(need(r_u, who, "r_u"));
     // both results are written field by field while later fields of u and B are still to be read
     auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
-        const double* pe = p + (int64_t)(nfld - 1) * ps + L->n_v;
-        const double* oe = o + (int64_t)(nfld - 1) * os + L->n_v;
-        return p < oe && o < pe;
+        return spans_meet(p, ps, o, os, nfld, L->n_v);
     };
     if (meets(r_B, rB_stride, r_u, ru_stride)) return fail(NKV_EINVAL, "%s: r_B overlaps r_u", who);
     if (meets(u, u_stride, r_B, rB_stride) || meets(B, B_stride, r_B, rB_stride))
         return fail(NKV_EINVAL, "%s: r_B overlaps u or B", who);
     if (meets(u, u_stride, r_u, ru_stride) || meets(B, B_stride, r_u, ru_stride))
         return fail(NKV_EINVAL, "%s: r_u overlaps u or B", who);
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_BT_RHS(NX)                                                                                              \
-    case NX:                                                                                                        \
-        if (ldim == 3)                                                                                              \
-            launch_tangent<3, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r_B, rB_stride, r_u, \
-                                  ru_stride, st);                                                                   \
-        else                                                                                                        \
-            launch_tangent<2, NX>(nel, nfld, D, w, xm, ym, zm, B, B_stride, kappa, u, u_stride, r_B, rB_stride, r_u, \
-                                  ru_stride, st);                                                                   \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_BT_RHS) }
-#undef NKV_BT_RHS
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        launch_tiled<LD, NX, 2>(k_burgers_tangent_rhs<LD, NX>, nel, S(stream), nfld, D, w, xm, ym, zm, B, B_stride,
+                                kappa, u, u_stride, r_B, rB_stride, r_u, ru_stride);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }
@@ -1577,9 +1238,9 @@ int nkv_burgers_backward_rhs(const nkv_layout* L, int lx1, int ldim, const doubl
                              int64_t S_stride, const double* kappa, const double* u, int nfld, int64_t u_stride,
                              double* r_X, int64_t rX_stride, double* r_u, int64_t ru_stride, void* stream) {
     static const char who[] = "burgers_backward_rhs";
-    CHECK(check_layout(L));
-    if (L->n_v == 0) return NKV_OK;   // an empty shard (more ranks than elements): nothing to touch
-    CHECK(check_mesh_args(who, L, lx1, ldim, zm));
+    int64_t nel;
+    CHECK(check_tiled_entry(who, L, lx1, ldim, D, w, xm, ym, zm, &nel));
+    if (nel == 0) return NKV_OK;   // an empty shard
     if (nfld < ldim) return fail(NKV_EINVAL, "%s: nfld=%d < ldim=%d (the first ldim fields of X and S advect)", who,
                                  nfld, ldim);
     if (X_stride < L->n_v || S_stride < L->n_v || u_stride < L->n_v || rX_stride < L->n_v || ru_stride < L->n_v)
@@ -1587,10 +1248,6 @@ int nkv_burgers_backward_rhs(const nkv_layout* L, int lx1, int ldim, const doubl
                     "%s: strides X_stride=%lld S_stride=%lld u_stride=%lld rX_stride=%lld ru_stride=%lld below n_v=%lld",
                     who, (long long)X_stride, (long long)S_stride, (long long)u_stride, (long long)rX_stride,
                     (long long)ru_stride, (long long)L->n_v);
-    CHECK(need(D, who, "D"));
-    CHECK(need(w, who, "w"));
-    CHECK(need(xm, who, "xm"));
-    CHECK(need(ym, who, "ym"));
     CHECK(need(X, who, "X"));
     CHECK(need(Sb, who, "S"));
     CHECK(need(kappa, who, "kappa"));
@@ -1600,29 +1257,18 @@ int nkv_burgers_backward_rhs(const nkv_layout* L, int lx1, int ldim, const doubl
     // both results are written field by field while later fields of X, S and u are still to be read; X and S
     // are only read and may be one state
     auto meets = [&](const double* p, int64_t ps, const double* o, int64_t os) {
-        const double* pe = p + (int64_t)(nfld - 1) * ps + L->n_v;
-        const double* oe = o + (int64_t)(nfld - 1) * os + L->n_v;
-        return p < oe && o < pe;
+        return spans_meet(p, ps, o, os, nfld, L->n_v);
     };
     if (meets(r_X, rX_stride, r_u, ru_stride)) return fail(NKV_EINVAL, "%s: r_X overlaps r_u", who);
     if (meets(X, X_stride, r_X, rX_stride) || meets(Sb, S_stride, r_X, rX_stride) || meets(u, u_stride, r_X, rX_stride))
         return fail(NKV_EINVAL, "%s: r_X overlaps X, S or u", who);
     if (meets(X, X_stride, r_u, ru_stride) || meets(Sb, S_stride, r_u, ru_stride) || meets(u, u_stride, r_u, ru_stride))
         return fail(NKV_EINVAL, "%s: r_u overlaps X, S or u", who);
-    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
-    const int64_t nel = L->n_v / pts;
-    hipStream_t st = S(stream);
-#define NKV_BB_RHS(NX)                                                                                               \
-    case NX:                                                                                                         \
-        if (ldim == 3)                                                                                               \
-            launch_backward<3, NX>(nel, nfld, D, w, xm, ym, zm, X, X_stride, Sb, S_stride, kappa, u, u_stride, r_X,   \
-                                   rX_stride, r_u, ru_stride, st);                                                   \
-        else                                                                                                         \
-            launch_backward<2, NX>(nel, nfld, D, w, xm, ym, zm, X, X_stride, Sb, S_stride, kappa, u, u_stride, r_X,   \
-                                   rX_stride, r_u, ru_stride, st);                                                   \
-        break;
-    switch (lx1) { NKV_PP_CASES(NKV_BB_RHS) }
-#undef NKV_BB_RHS
+    dispatch_tile(lx1, ldim, [&](auto ld, auto nx) {
+        constexpr int LD = decltype(ld)::value, NX = decltype(nx)::value;
+        launch_tiled<LD, NX, 2>(k_burgers_backward_rhs<LD, NX>, nel, S(stream), nfld, D, w, xm, ym, zm, X, X_stride, Sb,
+                                S_stride, kappa, u, u_stride, r_X, rX_stride, r_u, ru_stride);
+    });
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -335,22 +335,41 @@ constexpr int tile_threads() {
 inline int tile_epb(int pts) { return pts >= 256 ? 1 : 256 / pts; }
 constexpr int kMaxWaves = 16;   // 1024 threads (lx1 = 10 in 3-D: 1000 points)
 
-// This thread's point of the tile: its element, its three lines and its rows of D (LDS).
+// This thread's point of the tile: its element, its indices, its three lines, its rows and its columns of D (LDS).
+// The lines and rows take the point's indices from its offset r inside its element, as k_gradm1 does; i, j, k and
+// the columns take them from tid, where the element drops out because NX and NX^2 divide the points of an
+// element.  The values are the same.  Sharing one chain costs the tiled kernels of advdiff.hip registers at the
+// 4-wave budget (a column pointer off tid is rematerialised, one off r is kept live): CHANGELOG, "Shared element-tile
+// building blocks".
 template <int LDIM, int NX>
 struct TilePoint {
+    int i, j, k;                    // the point inside its element
     int ri, si, ti;                 // lines along r, s, t through the point
-    const double *Di, *Dj, *Dk;
+    const double *Di, *Dj, *Dk;     // rows of D: D(i, m) at Di[m]
+    const double *Ci, *Cj, *Ck;     // columns of D: D(m, i) at Ci[m*NX]
     __device__ __forceinline__ TilePoint(const double* D, int tid, int nt) {
         constexpr int pts = tile_pts<LDIM, NX>();
         const int le = tid / pts, r = tid - le * pts;
-        const int i = r % NX, j = (r / NX) % NX, k = LDIM == 3 ? r / (NX * NX) : 0;
+        const int ir = r % NX, jr = (r / NX) % NX, kr = LDIM == 3 ? r / (NX * NX) : 0;
         const int base = (tid < nt ? le : 0) * pts;   // lanes past the last whole element read element 0
-        ri = base + j * NX + k * NX * NX;
-        si = base + i + k * NX * NX;
-        ti = base + i + j * NX;
-        Di = D + i * NX;
-        Dj = D + j * NX;
-        Dk = D + k * NX;
+        ri = base + jr * NX + kr * NX * NX;
+        si = base + ir + kr * NX * NX;
+        ti = base + ir + jr * NX;
+        Di = D + ir * NX;
+        Dj = D + jr * NX;
+        Dk = D + kr * NX;
+        i = tid % NX;
+        j = (tid / NX) % NX;
+        k = LDIM == 3 ? (tid / (NX * NX)) % NX : 0;
+        Ci = D + i;
+        Cj = D + j;
+        Ck = D + k;
+    }
+    // The product of the point's GLL weights w_i w_j [w_k].
+    __device__ __forceinline__ double weight(const double* w) const {
+#pragma clang fp contract(off)
+        const double wij = w[i] * w[j];
+        return LDIM == 3 ? wij * w[k] : wij;
     }
 };
 
@@ -442,6 +461,29 @@ __device__ __forceinline__ void line_sums(const TilePoint<LDIM, NX>& q, const do
 #pragma unroll 2
         for (int m = 1; m < NX; ++m) ut = ut + U[q.ti + m * sk] * q.Dk[m];
     }
+}
+
+// The transpose of line_sums: sum_a D_a^T of the three flux tiles at this point,
+//   sum_m D(m, i) X(m, j, k) + sum_m D(m, j) Y(i, m, k) [+ sum_m D(m, k) Z(i, j, m)],  m ascending.
+template <int LDIM, int NX>
+__device__ __forceinline__ double transposed_line_sums(const TilePoint<LDIM, NX>& q, const double* X, const double* Y,
+                                                       const double* Z) {
+#pragma clang fp contract(off)
+    constexpr int sj = NX, sk = NX * NX;
+    double tr = q.Ci[0] * X[q.ri], ts = Y[q.si] * q.Cj[0];
+#pragma unroll 2
+    for (int m = 1; m < NX; ++m) {
+        tr = tr + q.Ci[m * NX] * X[q.ri + m];
+        ts = ts + Y[q.si + m * sj] * q.Cj[m * NX];
+    }
+    double acc = tr + ts;
+    if constexpr (LDIM == 3) {
+        double tt = Z[q.ti] * q.Ck[0];
+#pragma unroll 2
+        for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * q.Ck[m * NX];
+        acc = acc + tt;
+    }
+    return acc;
 }
 
 // The derivative along direction d exactly as k_gradm1 stores it: jacmi * acc.

@@ -238,7 +238,6 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
     constexpr int pts = tile_pts<LDIM, NX>();
-    constexpr int sj = NX, sk = NX * NX;
     constexpr int M = NX - 2;
     constexpr int ppts = pressure_pts<LDIM, NX>();
     const int nt = epb * pts;
@@ -259,10 +258,7 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
     const int le = tid / pts, rr = tid - le * pts;
     const int eb = le * pts;
     const bool intile = tid < nt;
-    const int pi = rr % NX, pj = (rr / NX) % NX, pk = LDIM == 3 ? rr / (NX * NX) : 0;
-    const double* Dci = h.D + pi;            // this point's columns of D: D(m, i) at Dci[m*NX]
-    const double* Dcj = h.D + pj;
-    const double* Dck = h.D + pk;
+    const int pi = q.i;
     for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
         const int64_t p = e0 * pts + tid;
         const bool live = intile && e0 + le < nel;
@@ -334,22 +330,7 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
                 if constexpr (LDIM == 3) Z[tid] = g[d][2] * s;
             }
             __syncthreads();
-            if (live) {
-                double tr = Dci[0] * X[q.ri], ts = Y[q.si] * Dcj[0];
-#pragma unroll 2
-                for (int m = 1; m < NX; ++m) {
-                    tr = tr + Dci[m * NX] * X[q.ri + m];
-                    ts = ts + Y[q.si + m * sj] * Dcj[m * NX];
-                }
-                double acc = tr + ts;
-                if constexpr (LDIM == 3) {
-                    double tt = Z[q.ti] * Dck[0];
-#pragma unroll 2
-                    for (int m = 1; m < NX; ++m) tt = tt + Z[q.ti + m * sk] * Dck[m * NX];
-                    acc = acc + tt;
-                }
-                t[d * t_stride + p] = acc;
-            }
+            if (live) t[d * t_stride + p] = transposed_line_sums<LDIM, NX>(q, X, Y, Z);
         }
     }
 }
