@@ -989,6 +989,39 @@ int nkv_pressure_cg_update(int64_t n, double* x, double* r, const double* p, con
                            void* stream);
 int nkv_pressure_partials(void);
 
+/* ---- the same three over two systems: the CG of both halves of a pair vector in one launch each -------
+ * A resolvent stage projects the re and the im half of a complex vector: two pressure solves on one mesh.  The
+ * systems share the coordinates, the factors, D, interp, gw and mult, which are staged and formed once per
+ * element group; the LDS tiles then serve system 0, then system 1 (LDS as the single-system kernels).  The
+ * systems come as separate pointers with one stride per operand, as in nkv_linconv_crhs: only 8-byte alignment
+ * is asked of either (in a pair vector the im half starts n_v doubles behind the re half, and n_v may be odd).
+ * active: bit s = system s, 1..3.  An inactive system is neither read nor written (its pointers may be NULL):
+ * not its vectors, nor its outputs, nor its partial rows.  For an active system every output and partial is
+ * bit for bit what the single-system entry gives on that system's operands alone: the same arithmetic in the
+ * same order, the same grid and the same slot per workgroup, no atomics, no contraction; element sub-ranges
+ * give the bits of the whole.  A system named in active with a NULL operand, and written spans that meet each
+ * other or a span that is read (strided fields segment by segment), are NKV_EINVAL.  Empty shards as above.
+ *
+ * nkv_pressure_div2:   out_s = nkv_pressure_div(u_s; mult); with pv_s and partials given (all active systems or
+ *   none) the three rows of system s go to partials + s * 3 NKV_PRESSURE_PARTIALS.
+ * nkv_pressure_gradt2: t_s = nkv_pressure_gradt(p_s); with res_s given (all active systems or none)
+ *   p_s <- first ? res_s : res_s + beta_s p_s, beta_s from the B values at rr_new + s*B over those at
+ *   rr_old + s*B.  first is shared.
+ * nkv_pressure_cg_update2: nkv_pressure_cg_update on (x_s, r_s, p_s, Ep_s) with the three rows of system s at
+ *   red + s * 3 Br, its r.r at rr_old + s*Bo, and its new partials written to rr_out + s * NKV_PRESSURE_PARTIALS:
+ *   its own mu and alpha.  inv_n, closed and init are shared. */
+int nkv_pressure_div2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                      const double* xm, const double* ym, const double* zm, const double* u0, const double* u1,
+                      int64_t u_stride, const double* mult, double* out0, double* out1, const double* pv0,
+                      const double* pv1, double* partials, int active, void* stream);
+int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                        const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
+                        const double* res1, const double* rr_new, const double* rr_old, int B, int first, double* t0,
+                        double* t1, int64_t t_stride, int active, void* stream);
+int nkv_pressure_cg_update2(int64_t n, double* x0, double* x1, double* r0, double* r1, const double* p0, const double* p1,
+                            const double* Ep0, const double* Ep1, const double* red, int Br, const double* rr_old, int Bo,
+                            double inv_n, int closed, int init, double* rr_out, int active, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

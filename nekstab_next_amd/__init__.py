@@ -28,7 +28,7 @@ def __getattr__(name):
         return getattr(importlib.import_module(".monitors", __name__), name)
     if name in ("AdvectionDiffusion", "box_boundary_mask", "mask_from_faces"):   # the model propagator (advdiff.py)
         return getattr(importlib.import_module(".advdiff", __name__), name)
-    if name in ("ResolventOperator", "CoupledResolventOperator", "pair_context"):   # the time-stepper resolvent over it (resolvent.py)
+    if name in ("ResolventOperator", "CoupledResolventOperator", "IncompressibleResolventOperator", "pair_context"):   # the time-stepper resolvent over it (resolvent.py)
         return getattr(importlib.import_module(".resolvent", __name__), name)
     if name in ("LinearisedConvection", "ViscousBurgers"):   # the nonlinear flow and its linearisation (burgers.py)
         return getattr(importlib.import_module(".burgers", __name__), name)

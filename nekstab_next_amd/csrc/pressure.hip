@@ -19,6 +19,9 @@
 // Every scalar stays on the device: a producer writes one partial per workgroup into a fixed slot, and every
 // workgroup of the consumer sums the slots in the same fixed order (cg_scalar), so all of them hold the same
 // bits and the same input gives the same bits run to run.
+// k_pressure_div2, k_pressure_gradt2 and k_pressure_cg_update2 run that iteration for two systems on one mesh (the
+// re and the im half of a pair vector: the projection inside a stage of the incompressible resolvent) in one launch
+// each, with the bits of the single-system kernels for either system; they stand behind the kernels above.
 #include "nkv_internal.h"
 
 namespace {
@@ -378,6 +381,314 @@ __global__ __launch_bounds__(kThreads) void k_pressure_cg_update(int64_t n, doub
     if (threadIdx.x == 0) rr_out[blockIdx.x] = s;
 }
 
+// ------------------------------------------------------------------------------------------
+// The two-system forms: the CG of two right-hand sides on one mesh (the re and the im half of a pair vector)
+// in one launch each.  The systems share the coordinates, the factors, D, I and w^: those are staged and formed
+// once per element group and the tiles then serve system 0, then system 1, so the LDS is the single-system
+// kernel's.  Per system the arithmetic, its order, the thread-to-point map, the grid and the slot of every
+// workgroup are those of the single-system kernel: the same bits.  active: bit s = system s; an inactive system
+// is neither read nor written.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_div2(
+    int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm, const double* u0,
+    const double* u1, int64_t u_stride, const double* __restrict__ mult, double* out0, double* out1, const double* pv0,
+    const double* pv1, double* __restrict__ partials, int active) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int M = NX - 2;
+    constexpr int ppts = pressure_pts<LDIM, NX>();
+    const int nt = epb * pts;
+    const Head<NX> h(lds, Dg, Ig, gwg);
+    const double* I = h.I;
+    double* X = h.tiles;
+    double* Y = X + nt;
+    double* Z = Y + nt;                      // 3-D only
+    const int tid = threadIdx.x;
+    const TilePoint<LDIM, NX> q(h.D, tid, nt);
+    const int le = tid / pts, rr = tid - le * pts;
+    const int eb = le * pts;
+    const bool intile = tid < nt;
+    const double* const us[2] = {u0, u1};
+    double* const outs[2] = {out0, out1};
+    const double* const pvs[2] = {pv0, pv1};
+    double s_pe[2] = {0.0, 0.0}, s_e[2] = {0.0, 0.0}, s_p[2] = {0.0, 0.0};
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = intile && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and the head is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+        const double m = live && mult ? mult[p] : 1.0;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (!(active >> s & 1)) continue;   // (uniform over the grid)
+            __syncthreads();   // every lane has formed its factors, the system before is interpolated: the tiles are free
+            if (live) {
+                double* tiles[3] = {X, Y, Z};
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    const double v = us[s][d * u_stride + p];
+                    tiles[d][tid] = mult ? m * v : v;
+                }
+            }
+            __syncthreads();
+            double dv = 0.0;
+            {
+                const double* tiles[3] = {X, Y, Z};
+#pragma unroll
+                for (int d = 0; d < LDIM; ++d) {
+                    double ur, us_, ut;
+                    line_sums<LDIM, NX>(q, tiles[d], ur, us_, ut);
+                    double t = g[d][0] * ur + g[d][1] * us_;
+                    if constexpr (LDIM == 3) t = t + g[d][2] * ut;
+                    dv = d == 0 ? t : dv + t;
+                }
+            }
+            __syncthreads();       // the velocity tiles are read
+            if (intile) X[tid] = dv;
+            __syncthreads();
+            // along r: X(i, j, k) -> Y(a, j, k), a < M
+            constexpr int n1 = LDIM == 3 ? M * NX * NX : M * NX;
+            if (intile && rr < n1) {
+                const int a = rr % M, row = rr / M;          // row = j + NX k
+                const double* src = X + eb + row * NX;
+                double acc = I[a * NX] * src[0];
+#pragma unroll 2
+                for (int mm = 1; mm < NX; ++mm) acc = acc + I[a * NX + mm] * src[mm];
+                Y[eb + rr] = acc;
+            }
+            __syncthreads();
+            // along s: Y(a, j, k) -> (a, b, k)
+            constexpr int n2 = LDIM == 3 ? M * M * NX : M * M;
+            double val = 0.0;
+            if (intile && rr < n2) {
+                const int a = rr % M, b = (rr / M) % M, k = rr / (M * M);
+                const double* src = Y + eb + a + M * NX * k;
+                double acc = I[b * NX] * src[0];
+#pragma unroll 2
+                for (int mm = 1; mm < NX; ++mm) acc = acc + I[b * NX + mm] * src[M * mm];
+                if constexpr (LDIM == 3) X[eb + rr] = acc;
+                val = acc;
+            }
+            if constexpr (LDIM == 3) {
+                __syncthreads();
+                // along t: X(a, b, k) -> (a, b, c)
+                if (intile && rr < ppts) {
+                    const int c = rr / (M * M), ab = rr - c * M * M;
+                    const double* src = X + eb + ab;
+                    double acc = I[c * NX] * src[0];
+#pragma unroll 2
+                    for (int mm = 1; mm < NX; ++mm) acc = acc + I[c * NX + mm] * src[M * M * mm];
+                    val = acc;
+                }
+            }
+            if (live && rr < ppts) {
+                const int a = rr % M, b = (rr / M) % M, c = LDIM == 3 ? rr / (M * M) : 0;
+                const double wab = h.gw[a] * h.gw[b];
+                const double wq = LDIM == 3 ? wab * h.gw[c] : wab;
+                const double o = wq * val;
+                const int64_t pp = (e0 + le) * ppts + rr;
+                outs[s][pp] = o;
+                if (partials) {
+                    const double pe = pvs[s][pp];
+                    s_pe[s] += pe * o;
+                    s_e[s] += o;
+                    s_p[s] += pe;
+                }
+            }
+        }
+    }
+    if (partials) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (!(active >> s & 1)) continue;
+            block_sum3(s_pe[s], s_e[s], s_p[s], h.red);
+            if (tid == 0) {
+                double* part = partials + (int64_t)s * 3 * kPB;
+                part[blockIdx.x] = s_pe[s];
+                part[kPB + blockIdx.x] = s_e[s];
+                part[2 * kPB + blockIdx.x] = s_p[s];
+            }
+        }
+    }
+}
+
+template <int LDIM, int NX>
+__global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt2(
+    int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
+    const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm, double* p0, double* p1,
+    const double* res0, const double* res1, const double* __restrict__ rr_new, const double* __restrict__ rr_old, int B,
+    int first, double* t0, double* t1, int64_t t_stride, int active) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int pts = tile_pts<LDIM, NX>();
+    constexpr int M = NX - 2;
+    constexpr int ppts = pressure_pts<LDIM, NX>();
+    const int nt = epb * pts;
+    const Head<NX> h(lds, Dg, Ig, gwg);
+    const double* I = h.I;
+    double* X = h.tiles;
+    double* Y = X + nt;
+    double* Z = Y + nt;                      // 3-D only
+    double* A = LDIM == 3 ? Z + nt : Z;
+    double* Bt = A + nt;
+    const int tid = threadIdx.x;
+    double* const pins[2] = {p0, p1};
+    const double* const ress[2] = {res0, res1};
+    double* const ts[2] = {t0, t1};
+    const bool with_res = res0 || res1;
+    double beta[2] = {0.0, 0.0};
+    if (with_res && !first) {   // (uniform over the grid)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (!(active >> s & 1)) continue;
+            const double num = cg_scalar(rr_new + (int64_t)s * B, B, h.red + 2 * s);
+            const double den = cg_scalar(rr_old + (int64_t)s * B, B, h.red + 2 * s + 1);
+            beta[s] = den != 0.0 ? num / den : 0.0;
+        }
+    }
+    const TilePoint<LDIM, NX> q(h.D, tid, nt);
+    const int le = tid / pts, rr = tid - le * pts;
+    const int eb = le * pts;
+    const bool intile = tid < nt;
+    const int pi = q.i;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const int64_t p = e0 * pts + tid;
+        const bool live = intile && e0 + le < nel;
+        __syncthreads();   // the previous group's reads are done (and the head is staged on the first pass)
+        if (live) {
+            X[tid] = xm[p];
+            Y[tid] = ym[p];
+            if (LDIM == 3) Z[tid] = zm[p];
+        }
+        __syncthreads();
+        double g[3][3], jac;   // dead lanes compute garbage they never store
+        geometric_factors_jac<LDIM, NX>(q, X, Y, Z, g, jac);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (!(active >> s & 1)) continue;   // (uniform over the grid)
+            // (the interpolation tiles were last read before the barriers of the flux loop of the system before)
+            if (live && rr < ppts) {
+                const int a = rr % M, b = (rr / M) % M, c = LDIM == 3 ? rr / (M * M) : 0;
+                const double wab = h.gw[a] * h.gw[b];
+                const double wq = LDIM == 3 ? wab * h.gw[c] : wab;
+                const int64_t pp = (e0 + le) * ppts + rr;
+                double v;
+                if (with_res) {
+                    v = first ? ress[s][pp] : ress[s][pp] + beta[s] * pins[s][pp];
+                    pins[s][pp] = v;
+                } else {
+                    v = pins[s][pp];
+                }
+                A[eb + rr] = wq * v;
+            }
+            __syncthreads();   // w^ p is staged; every lane has formed its factors, the fluxes of the system before are read
+            double* S1 = A;        // the tile the transposed s pass reads
+            double* S2 = Bt;       // ... and writes
+            if constexpr (LDIM == 3) {
+                // along t, transposed: A(a, b, c) -> Bt(a, b, k)
+                if (intile && rr < M * M * NX) {
+                    const int k = rr / (M * M), ab = rr - k * M * M;
+                    const double* src = A + eb + ab;
+                    double acc = I[k] * src[0];
+#pragma unroll 2
+                    for (int c = 1; c < M; ++c) acc = acc + I[c * NX + k] * src[M * M * c];
+                    Bt[eb + rr] = acc;
+                }
+                __syncthreads();
+                S1 = Bt;
+                S2 = A;
+            }
+            // along s, transposed: S1(a, b, k) -> S2(a, j, k)
+            constexpr int n2 = LDIM == 3 ? M * NX * NX : M * NX;
+            if (intile && rr < n2) {
+                const int a = rr % M, j = (rr / M) % NX, k = rr / (M * NX);
+                const double* src = S1 + eb + a + M * M * k;
+                double acc = I[j] * src[0];
+#pragma unroll 2
+                for (int b = 1; b < M; ++b) acc = acc + I[b * NX + j] * src[M * b];
+                S2[eb + rr] = acc;
+            }
+            __syncthreads();
+            // along r, transposed: S2(a, j, k) -> the GLL point (i, j, k)
+            double sv = 0.0;
+            if (intile) {
+                const double* src = S2 + eb + M * (rr / NX);
+                sv = I[pi] * src[0];
+#pragma unroll 2
+                for (int a = 1; a < M; ++a) sv = sv + I[a * NX + pi] * src[a];
+            }
+#pragma unroll
+            for (int d = 0; d < LDIM; ++d) {
+                if (d > 0) __syncthreads();   // the previous direction's fluxes are read
+                if (intile) {
+                    X[tid] = g[d][0] * sv;
+                    Y[tid] = g[d][1] * sv;
+                    if constexpr (LDIM == 3) Z[tid] = g[d][2] * sv;
+                }
+                __syncthreads();
+                if (live) ts[s][d * t_stride + p] = transposed_line_sums<LDIM, NX>(q, X, Y, Z);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_pressure_cg_update2(
+    int64_t n, double* x0, double* x1, double* r0, double* r1, const double* p0, const double* p1, const double* Ep0,
+    const double* Ep1, const double* __restrict__ red, int Br, const double* __restrict__ rr_old, int Bo, double inv_n,
+    int closed, int init, double* __restrict__ rr_out, int active) {
+#pragma clang fp contract(off)
+    __shared__ double sc2[16];
+    double* const xs[2] = {x0, x1};
+    double* const rs[2] = {r0, r1};
+    const double* const ps[2] = {p0, p1};
+    const double* const Eps[2] = {Ep0, Ep1};
+    const int64_t step = (int64_t)gridDim.x * kThreads;
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy) {
+        if (!(active >> sy & 1)) continue;   // (uniform over the grid)
+        double* sc = sc2 + 8 * sy;
+        const double* rd = red + (int64_t)sy * 3 * Br;
+        double* x = xs[sy];
+        double* r = rs[sy];
+        const double* p = ps[sy];
+        const double* Ep = Eps[sy];
+        const double s_e = closed ? cg_scalar(rd + Br, Br, sc) : 0.0;
+        const double mu = s_e * inv_n;
+        double alpha = 0.0;
+        if (!init) {
+            const double p_e = cg_scalar(rd, Br, sc + 1), s_p = cg_scalar(rd + 2 * (int64_t)Br, Br, sc + 2);
+            const double rr = cg_scalar(rr_old + (int64_t)sy * Bo, Bo, sc + 3);
+            const double den = p_e - mu * s_p;
+            alpha = den != 0.0 ? rr / den : 0.0;
+        }
+        double s = 0.0;
+        for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += step) {
+            double rv;
+            if (init) {
+                x[i] = 0.0;
+                rv = Ep[i] - mu;
+            } else {
+                x[i] = x[i] + alpha * p[i];
+                rv = r[i] - alpha * (Ep[i] - mu);
+            }
+            r[i] = rv;
+            s += rv * rv;
+        }
+        s = block_sum(s, sc + 4);
+        if (threadIdx.x == 0) rr_out[(int64_t)sy * kPB + blockIdx.x] = s;
+    }
+}
+
 template <int LDIM, int NX>
 void launch_div(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
                 const double* zm, const double* u, int64_t u_stride, const double* mult, double* out, const double* pv,
@@ -403,6 +714,71 @@ void launch_gradt(int64_t nel, const double* D, const double* I, const double* g
     const int grid = (int)std::min<int64_t>(groups, 4 * kPB);
     hipLaunchKernelGGL((k_pressure_gradt<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
                        gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride);
+}
+
+// The two-system launches: the grids, the block sizes and the LDS of launch_div and launch_gradt.
+template <int LDIM, int NX>
+void launch_div2(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
+                 const double* zm, const double* u0, const double* u1, int64_t u_stride, const double* mult, double* out0,
+                 double* out1, const double* pv0, const double* pv1, double* partials, int active, hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)LDIM * epb * pts);
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, kPB);
+    hipLaunchKernelGGL((k_pressure_div2<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
+                       gw, xm, ym, zm, u0, u1, u_stride, mult, out0, out1, pv0, pv1, partials, active);
+}
+
+template <int LDIM, int NX>
+void launch_gradt2(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
+                   const double* zm, double* p0, double* p1, const double* res0, const double* res1, const double* rr_new,
+                   const double* rr_old, int B, int first, double* t0, double* t1, int64_t t_stride, int active,
+                   hipStream_t st) {
+    constexpr int pts = tile_pts<LDIM, NX>();
+    const int epb = tile_epb(pts);
+    const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)(LDIM + 2) * epb * pts);
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, 4 * kPB);
+    hipLaunchKernelGGL((k_pressure_gradt2<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
+                       gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0, t1, t_stride, active);
+}
+
+// The spans a two-system entry writes and reads (NULL operands are left out): no written span may meet another
+// written span or a read one.  In a pair vector the halves interleave, so strided fields enter segment by segment.
+struct Spans {
+    struct One {
+        const double* p;
+        int64_t n;
+        const char* name;
+    };
+    One out[10], in[14];
+    int n_out = 0, n_in = 0;
+    void add(One* list, int& cnt, const double* p, int64_t n, const char* name, int nfld = 1, int64_t stride = 0) {
+        for (int f = 0; p && f < nfld; ++f) list[cnt++] = One{p + (int64_t)f * stride, n, name};
+    }
+    void writes(const double* p, int64_t n, const char* name, int nfld = 1, int64_t stride = 0) {
+        add(out, n_out, p, n, name, nfld, stride);
+    }
+    void reads(const double* p, int64_t n, const char* name, int nfld = 1, int64_t stride = 0) {
+        add(in, n_in, p, n, name, nfld, stride);
+    }
+    int check(const char* who) const {
+        auto meet = [](const One& a, const One& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
+        for (int i = 0; i < n_out; ++i) {
+            for (int j = i + 1; j < n_out; ++j)
+                if (meet(out[i], out[j]))
+                    return fail(NKV_EINVAL, "%s: %s overlaps %s", who, out[i].name, out[j].name);
+            for (int j = 0; j < n_in; ++j)
+                if (meet(out[i], in[j])) return fail(NKV_EINVAL, "%s: %s overlaps %s", who, out[i].name, in[j].name);
+        }
+        return NKV_OK;
+    }
+};
+
+int check_active(const char* who, int active) {
+    if (active < 1 || active > 3) return fail(NKV_EINVAL, "%s: active=%d outside 1..3 (bit s = system s)", who, active);
+    return NKV_OK;
 }
 
 int check_pressure_args(const char* who, const nkv_layout* L, int lx1, int ldim, const double* zm) {
@@ -512,6 +888,177 @@ int nkv_pressure_cg_update(int64_t n, double* x, double* r, const double* p, con
     const int grid = grid_for(n, kPB);
     hipLaunchKernelGGL(k_pressure_cg_update, dim3(grid), dim3(kThreads), 0, S(stream), n, x, r, p, Ep, red, Br, rr_old, Bo,
                        inv_n, closed, init, rr_out);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_div2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                      const double* xm, const double* ym, const double* zm, const double* u0, const double* u1,
+                      int64_t u_stride, const double* mult, double* out0, double* out1, const double* pv0,
+                      const double* pv1, double* partials, int active, void* stream) {
+    static const char who[] = "pressure_div2";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch (its partial slots stay as they are)
+    CHECK(check_pressure_args(who, L, lx1, ldim, zm));
+    CHECK(check_active(who, active));
+    if (u_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: stride u_stride=%lld below n_v=%lld", who, (long long)u_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(interp, who, "interp"));
+    CHECK(need(gw, who, "gw"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    const int64_t npz = nel * (ldim == 3 ? (lx1 - 2) * (lx1 - 2) * (lx1 - 2) : (lx1 - 2) * (lx1 - 2));
+    static const char* const un[2] = {"u0", "u1"};
+    static const char* const on[2] = {"out0", "out1"};
+    static const char* const pn[2] = {"pv0", "pv1"};
+    const double* const us[2] = {u0, u1};
+    double* const outs[2] = {out0, out1};
+    const double* const pvs[2] = {pv0, pv1};
+    Spans sp;
+    sp.reads(mult, L->n_v, "mult");
+    for (int s = 0; s < 2; ++s) {
+        if (!(active >> s & 1)) continue;
+        CHECK(need(us[s], who, un[s]));
+        CHECK(need(outs[s], who, on[s]));
+        if (!pvs[s] != !partials)
+            return fail(NKV_EINVAL, "%s: %s and partials are both NULL or neither", who, pn[s]);
+        sp.reads(us[s], L->n_v, un[s], ldim, u_stride);
+        sp.reads(pvs[s], npz, pn[s]);
+        sp.writes(outs[s], npz, on[s]);
+        if (partials) sp.writes(partials + (int64_t)s * 3 * kPB, 3 * kPB, "partials");
+    }
+    CHECK(sp.check(who));
+    hipStream_t st = S(stream);
+#define NKV_PR_DIV2(NX)                                                                                          \
+    case NX:                                                                                                     \
+        if (ldim == 3)                                                                                           \
+            launch_div2<3, NX>(nel, D, interp, gw, xm, ym, zm, u0, u1, u_stride, mult, out0, out1, pv0, pv1,     \
+                               partials, active, st);                                                            \
+        else                                                                                                     \
+            launch_div2<2, NX>(nel, D, interp, gw, xm, ym, zm, u0, u1, u_stride, mult, out0, out1, pv0, pv1,     \
+                               partials, active, st);                                                            \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_DIV2) }
+#undef NKV_PR_DIV2
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                        const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
+                        const double* res1, const double* rr_new, const double* rr_old, int B, int first, double* t0,
+                        double* t1, int64_t t_stride, int active, void* stream) {
+    static const char who[] = "pressure_gradt2";
+    CHECK(check_layout(L));
+    if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
+    CHECK(check_pressure_args(who, L, lx1, ldim, zm));
+    CHECK(check_active(who, active));
+    if (t_stride < L->n_v)
+        return fail(NKV_EINVAL, "%s: stride t_stride=%lld below n_v=%lld", who, (long long)t_stride, (long long)L->n_v);
+    CHECK(need(D, who, "D"));
+    CHECK(need(interp, who, "interp"));
+    CHECK(need(gw, who, "gw"));
+    CHECK(need(xm, who, "xm"));
+    CHECK(need(ym, who, "ym"));
+    const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
+    const int64_t nel = L->n_v / pts;
+    const int64_t npz = nel * (ldim == 3 ? (lx1 - 2) * (lx1 - 2) * (lx1 - 2) : (lx1 - 2) * (lx1 - 2));
+    static const char* const pn[2] = {"p0", "p1"};
+    static const char* const rn[2] = {"res0", "res1"};
+    static const char* const tn[2] = {"t0", "t1"};
+    double* const ps[2] = {p0, p1};
+    const double* const ress[2] = {res0, res1};
+    double* const ts[2] = {t0, t1};
+    const bool with_res = ress[active & 1 ? 0 : 1] != nullptr;   // decided by the first active system
+    Spans sp;
+    for (int s = 0; s < 2; ++s) {
+        if (!(active >> s & 1)) continue;
+        CHECK(need(ps[s], who, pn[s]));
+        CHECK(need(ts[s], who, tn[s]));
+        if ((ress[s] != nullptr) != with_res)
+            return fail(NKV_EINVAL, "%s: res0 and res1 of the active systems are both NULL or neither", who);
+        sp.writes(ts[s], L->n_v, tn[s], ldim, t_stride);
+        if (with_res) {
+            sp.writes(ps[s], npz, pn[s]);
+            sp.reads(ress[s], npz, rn[s]);
+        } else {
+            sp.reads(ps[s], npz, pn[s]);
+        }
+    }
+    if (with_res && !first) {
+        CHECK(need(rr_new, who, "rr_new"));
+        CHECK(need(rr_old, who, "rr_old"));
+        if (B < 1 || B > kPB) return fail(NKV_EINVAL, "%s: B=%d outside 1..%d", who, B, kPB);
+        sp.reads(rr_new, 2 * (int64_t)B, "rr_new");
+        sp.reads(rr_old, 2 * (int64_t)B, "rr_old");
+    }
+    CHECK(sp.check(who));
+    if (!(active & 1)) res0 = nullptr;   // the kernel takes the res path when either is given
+    if (!(active & 2)) res1 = nullptr;
+    hipStream_t st = S(stream);
+#define NKV_PR_GT2(NX)                                                                                              \
+    case NX:                                                                                                         \
+        if (ldim == 3)                                                                                               \
+            launch_gradt2<3, NX>(nel, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0,   \
+                                 t1, t_stride, active, st);                                                          \
+        else                                                                                                         \
+            launch_gradt2<2, NX>(nel, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0,   \
+                                 t1, t_stride, active, st);                                                          \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_GT2) }
+#undef NKV_PR_GT2
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_cg_update2(int64_t n, double* x0, double* x1, double* r0, double* r1, const double* p0, const double* p1,
+                            const double* Ep0, const double* Ep1, const double* red, int Br, const double* rr_old, int Bo,
+                            double inv_n, int closed, int init, double* rr_out, int active, void* stream) {
+    static const char who[] = "pressure_cg_update2";
+    if (n < 0) return fail(NKV_EINVAL, "%s: n=%lld", who, (long long)n);
+    CHECK(check_active(who, active));
+    CHECK(need(rr_out, who, "rr_out"));
+    if (!init) {
+        CHECK(need(red, who, "red"));
+        CHECK(need(rr_old, who, "rr_old"));
+        if (Bo < 1 || Bo > kPB) return fail(NKV_EINVAL, "%s: Bo=%d outside 1..%d", who, Bo, kPB);
+    }
+    if (closed) CHECK(need(red, who, "red"));
+    if ((closed || !init) && (Br < 1 || Br > kPB)) return fail(NKV_EINVAL, "%s: Br=%d outside 1..%d", who, Br, kPB);
+    if (!std::isfinite(inv_n)) return fail(NKV_EINVAL, "%s: inv_n=%g", who, inv_n);
+    static const char* const xn[2] = {"x0", "x1"};
+    static const char* const rn[2] = {"r0", "r1"};
+    static const char* const pn[2] = {"p0", "p1"};
+    static const char* const en[2] = {"Ep0", "Ep1"};
+    double* const xs[2] = {x0, x1};
+    double* const rs[2] = {r0, r1};
+    const double* const ps[2] = {p0, p1};
+    const double* const Eps[2] = {Ep0, Ep1};
+    Spans sp;
+    for (int s = 0; s < 2; ++s) {
+        if (!(active >> s & 1)) continue;
+        if (n > 0) {
+            CHECK(need(xs[s], who, xn[s]));
+            CHECK(need(rs[s], who, rn[s]));
+            CHECK(need(Eps[s], who, en[s]));
+            if (!init) CHECK(need(ps[s], who, pn[s]));
+            sp.writes(xs[s], n, xn[s]);
+            sp.writes(rs[s], n, rn[s]);
+            sp.reads(Eps[s], n, en[s]);
+            if (!init) sp.reads(ps[s], n, pn[s]);
+        }
+        sp.writes(rr_out + (int64_t)s * kPB, kPB, "rr_out");
+        if (closed || !init) sp.reads(red + (int64_t)s * 3 * Br, 3 * (int64_t)Br, "red");
+        if (!init) sp.reads(rr_old + (int64_t)s * Bo, Bo, "rr_old");
+    }
+    CHECK(sp.check(who));
+    // (an empty shard still launches one workgroup: it writes a zero partial for every active system)
+    const int grid = grid_for(n, kPB);
+    hipLaunchKernelGGL(k_pressure_cg_update2, dim3(grid), dim3(kThreads), 0, S(stream), n, x0, x1, r0, r1, p0, p1, Ep0, Ep1,
+                       red, Br, rr_old, Bo, inv_n, closed, init, rr_out, active);
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -18,9 +18,11 @@ state, and the Jacobian of ``Φ`` there is exactly the linear operator.  ``newto
 ``LegacyMatvec(3.2, ·)``, ``svds`` and ``transient_growth_analysis`` run on these unchanged.
 
 Each stage forms ``k = minv · r`` with ``nkv_advdiff_stage``, projects its velocity rows in place (a CG solve:
-pressure.py) and closes with the parent's stage kernel, the mask standing in for ``minv``.  ``OrbitFlow`` and
-the resolvents drive the right-hand sides and their own stages and would skip the projection: they refuse
-these classes.
+pressure.py) and closes with the parent's stage kernel, the mask standing in for ``minv``.  ``OrbitFlow``,
+``ResolventOperator`` and ``CoupledResolventOperator`` drive the right-hand sides and their own stages and would
+skip the projection: they refuse these classes.  The resolvent over a :class:`LinearisedNavierStokes` is
+:class:`~nekstab_next_amd.resolvent.IncompressibleResolventOperator`, which projects the re and the im half of
+every stage in one two-system CG (``DivergenceFreeProjector.project_pair_ptr``).
 """
 from __future__ import annotations
 
@@ -119,8 +121,8 @@ def refuse_incompressible(who: str, model) -> None:
             isinstance(getattr(model, "lin", None), LinearisedNavierStokes):
         raise ValueError(f"{who}: a {type(model).__name__} is refused: {who} steps with the unprojected right-hand "
                          f"sides and would silently skip the divergence-free projection of IncompressibleFlow / "
-                         f"LinearisedNavierStokes; orbits and resolvents over the incompressible flow are not "
-                         f"implemented")
+                         f"LinearisedNavierStokes; IncompressibleResolventOperator is the resolvent over a "
+                         f"LinearisedNavierStokes, orbits over the incompressible flow are not implemented")
 
 
 __all__ = ["IncompressibleFlow", "LinearisedNavierStokes", "refuse_incompressible"]

@@ -25,6 +25,13 @@ One CG iteration is three launches and one ``dsavg`` batch of ``ldim`` segments:
 ``Σp``, ``nkv_pressure_cg_update`` forms ``α``, updates ``x`` and ``r`` and emits the partials of ``rᵀr``.
 ``α`` and ``β`` never leave the device; the host reads one scalar every ``check_every`` iterations.  The
 reductions run in a fixed order without atomics: the same input gives the same bits.
+
+``project_pair_ptr`` solves two systems on the mesh at once, the re and the im half of a pair vector (a resolvent
+stage): the same iteration over ``nkv_pressure_gradt2``, ``nkv_pressure_div2`` and ``nkv_pressure_cg_update2``, which
+stage the coordinates and form the factors once for both, one ``dsavg`` batch of ``2·ldim`` segments and one
+all-reduce per reduced quantity.  Every system keeps its own scalars and its own stop; one that has met it is
+frozen (dropped from the ``active`` mask of every later launch), so each result carries the bits and the iteration
+count of ``project_ptr`` on it alone.
 """
 from __future__ import annotations
 
@@ -52,7 +59,9 @@ class DivergenceFreeProjector:
     ``2·npz_global + 20``) raise ``RuntimeError``.  ``closed``: ``"auto"``, True or False.
 
     ``apply(x, y)`` projects the velocity rows of a state vector; ``last_iterations`` is the count of the latest
-    solve and ``phi`` its multiplier (this rank's ``nel·lx2^ldim`` values)."""
+    solve and ``phi`` its multiplier (this rank's ``nel·lx2^ldim`` values).  ``project_pair_ptr`` projects two
+    velocities in one CG loop; ``last_iterations_each`` holds its two counts and ``last_iterations`` their maximum
+    (``phi`` stays the latest single solve's)."""
 
     def __init__(self, ctx: NekContext, coords: dict | None = None, mask=None, face_average="auto", tol: float = 1e-12,
                  maxiter: int | None = None, check_every: int = 8, closed="auto", operator: AdvectionDiffusion | None = None):
@@ -99,6 +108,8 @@ class DivergenceFreeProjector:
         self._chk = torch.zeros(1, **f64)                            # the scalar the host reads (allocated once)
         self.phi = self._x[: self.npz]
         self.last_iterations = 0
+        self.last_iterations_each = (0, 0)                           # of the latest two-system solve
+        self._pair = None                                            # the buffers of project_pair_ptr
         self.closed_ratio = None
         self.closed = False
         if closed == "auto":
@@ -209,6 +220,114 @@ class DivergenceFreeProjector:
         self._gradt(self._x)
         ctx.call("nkv_advdiff_stage", v_ptr, lay.sv, minv.data_ptr(), self._t.data_ptr(), lay.sv, -1.0, out_ptr, lay.sv,
                  lay.ldim, 0, ctx.stream)
+
+    # ---- the solve of two systems at once ----
+    def _pair_buffers(self):
+        """The second set of CG vectors, allocated on first use: x, r, p, Ep, D^T p and the partial rows of both
+        systems (system 0's too: the two-system entries take the rows of both from one buffer)."""
+        if self._pair is None:
+            lay, B = self.ctx.layout, self.PARTIALS
+            f64 = dict(dtype=torch.float64, device=self.ctx.device)
+            npad = max(self.npz, 2)
+            x, r, p, Ep = (torch.zeros(2, npad, **f64) for _ in range(4))
+            t = torch.zeros(2 * lay.ldim * lay.sv + 2, **f64)        # system s, component c at (s ldim + c) sv
+            red = torch.zeros(2 * 3 * B, **f64)
+            rr = [torch.zeros(2 * B, **f64) for _ in range(2)]
+            t_ptrs = [t.data_ptr() + 8 * k * lay.sv for k in range(2 * lay.ldim)]
+            t_sets = {1: t_ptrs[: lay.ldim], 2: t_ptrs[lay.ldim:], 3: t_ptrs}   # by ``active``
+            self._pair = dict(x=x, r=r, p=p, Ep=Ep, t=t, red=red, rr=rr, t_sets=t_sets, chk=torch.zeros(2, **f64))
+        return self._pair
+
+    def _reduced2(self, part: torch.Tensor, rows: int):
+        """``_reduced`` for the rows of both systems: one all-reduce covers them."""
+        if self._world == 1:
+            return part, self.PARTIALS
+        s = part.view(2 * rows, self.PARTIALS).sum(dim=1)
+        self.ctx.comm.allreduce_(s)
+        return s, 1
+
+    def _host_sums2(self, part: torch.Tensor, B: int):
+        """The two scalars the host reads in one copy: the sums of both systems' partials of r.r."""
+        w = self._pair["chk"]
+        torch.sum(part.view(2, B), dim=1, out=w)
+        a, b = w.tolist()
+        return [a, b]
+
+    def project_pair_ptr(self, v0_ptr: int, v1_ptr: int, stride: int, out0_ptr: int | None = None,
+                         out1_ptr: int | None = None) -> None:
+        """``P`` on the ``ldim`` segments at ``v0_ptr`` and on those at ``v1_ptr`` (stride ``stride`` doubles,
+        ``n_v`` points of the base layout each: the halves of a pair vector), into ``out0_ptr`` / ``out1_ptr``
+        (default: in place).  One CG loop over the two-system entries (``nkv_pressure_div2``, ``_gradt2``,
+        ``_cg_update2``): one ``dsavg`` batch of ``2·ldim`` segments and one all-reduce per reduced quantity and
+        iteration, both residuals read together every ``check_every`` iterations.  Each system has its own ``‖b‖``
+        and stop; one that meets it at a check (or has ``b = 0``) is frozen, its bit cleared from ``active`` for
+        every later launch, so each result is bit for bit ``project_ptr``'s for it alone on one rank, with the same
+        count (``last_iterations_each``; ``last_iterations`` is their maximum)."""
+        ctx, lay = self.ctx, self.ctx.layout
+        out0_ptr = v0_ptr if out0_ptr is None else out0_ptr
+        out1_ptr = v1_ptr if out1_ptr is None else out1_ptr
+        w, minv, d, sv, st = self._pair_buffers(), self.op._minv, lay.ldim, lay.sv, ctx.stream
+        x, r, p, Ep = ([a[0].data_ptr(), a[1].data_ptr()] for a in (w["x"], w["r"], w["p"], w["Ep"]))
+        tp = [w["t"].data_ptr(), w["t"].data_ptr() + 8 * d * sv]
+        redp = w["red"].data_ptr()
+        inv_n, closed = 1.0 / max(self.npz_global, 1), int(self.closed)
+
+        def div2(u0, u1, ustride, mult, active):
+            ctx.call("nkv_pressure_div2", *self._head, u0, u1, ustride, mult, *Ep, *p, redp, active, st)
+
+        def gradt2(src, res, rr_new, rr_old, B, first, active):
+            ctx.call("nkv_pressure_gradt2", *self._head, *src, *res, rr_new, rr_old, B, int(first), *tp, sv, active, st)
+            average_segments(self.op.face_average, w["t_sets"][active])
+
+        def update2(red, Br, rr_old, Bo, rr_out, init, active):
+            ctx.call_nl("nkv_pressure_cg_update2", self.npz, *x, *r, *p, *Ep, None if red is None else red.data_ptr(),
+                        Br, None if rr_old is None else rr_old.data_ptr(), Bo, inv_n, closed, int(init),
+                        rr_out.data_ptr(), active, st)
+
+        # b = Z D v; x = 0, r = b
+        div2(v0_ptr, v1_ptr, stride, None, 3)
+        red, Br = self._reduced2(w["red"], 3)
+        update2(red, Br, None, 1, w["rr"][0], True, 3)
+        rr, Bo = self._reduced2(w["rr"][0], 1)
+        bb = self._host_sums2(rr, Bo)
+        if not all(math.isfinite(b) for b in bb):
+            raise RuntimeError("DivergenceFreeProjector: the divergence of the input is not finite")
+        stop = [(self.tol ** 2) * b for b in bb]
+        its = [0, 0]
+        active = sum(1 << s for s in range(2) if bb[s] > 0.0)
+        it, rr_prev = 0, None
+        while active:
+            if it >= self.maxiter:
+                self.last_iterations_each, self.last_iterations = tuple(its), max(its)
+                now = self._host_sums2(rr, Bo)
+                rel = max(math.sqrt(max(now[s], 0.0) / bb[s]) for s in range(2) if active >> s & 1)
+                raise RuntimeError(f"DivergenceFreeProjector: CG did not reach tol={self.tol:g} in maxiter={self.maxiter} "
+                                   f"iterations (|r|/|b| = {rel:.3e})")
+            gradt2(p, r, rr.data_ptr(), None if rr_prev is None else rr_prev.data_ptr(), Bo, it == 0, active)
+            div2(*tp, sv, minv.data_ptr(), active)
+            red, Br = self._reduced2(w["red"], 3)
+            out = w["rr"][(it + 1) % 2]
+            update2(red, Br, rr, Bo, out, False, active)
+            rr_prev = rr
+            rr, Bo = self._reduced2(out, 1)
+            it += 1
+            for s in range(2):
+                if active >> s & 1:
+                    its[s] = it
+            if it % self.check_every == 0:
+                now = self._host_sums2(rr, Bo)
+                for s in range(2):
+                    if not active >> s & 1:
+                        continue
+                    if not math.isfinite(now[s]):
+                        raise RuntimeError("DivergenceFreeProjector: the CG residual is not finite")
+                    if now[s] <= stop[s]:
+                        active &= ~(1 << s)
+        self.last_iterations_each, self.last_iterations = tuple(its), max(its)
+        # out = v - minv dsavg(D^T x)   (x = 0 when b = 0: out = v)
+        gradt2(x, (None, None), None, None, 1, True, 3)
+        for v_ptr, t_ptr, o_ptr in ((v0_ptr, tp[0], out0_ptr), (v1_ptr, tp[1], out1_ptr)):
+            ctx.call("nkv_advdiff_stage", v_ptr, stride, minv.data_ptr(), t_ptr, sv, -1.0, o_ptr, stride, d, 0, st)
 
     def apply(self, x: NekVector, y: NekVector | None = None) -> NekVector:
         """``y = x`` with its velocity rows projected (in place when ``y`` is None); every other row is copied."""

@@ -27,7 +27,9 @@ deviations from the reference's real-state form are DESIGN §3's.
 
 :class:`CoupledResolventOperator` is the same algorithm about a base state ``B``: ``L = L_B`` of
 :class:`~nekstab_next_amd.burgers.LinearisedConvection`, production term ``(u'·∇)B`` included, the non-normal
-part that makes resolvent gains large.
+part that makes resolvent gains large.  :class:`IncompressibleResolventOperator` is that operator over a
+:class:`~nekstab_next_amd.incompressible.LinearisedNavierStokes`: ``L = P L_B`` on the divergence-free velocities,
+the projection of both halves of every stage in one two-system pressure CG.
 
 Stability: every ``dt · (lambda - i omega)``, lambda in the spectrum of L, inside RK4's region, roughly
 ``dt · rho(L - i omega) <~ 2.78``.  On the edge of that region phi vanishes (z = -2.785 and
@@ -80,11 +82,16 @@ class ResolventOperator(LinearOperator):
     are its basis size and restarts.  An inner solve that does not converge raises ``RuntimeError``.
     ``last_gmres``: ``{"info", "residuals", "adjoint"}`` of the latest solve."""
 
+    # Whether the class projects every stage onto the divergence-free velocities: one that does not refuses the
+    # incompressible models, whose projection it would silently skip.
+    projects_stages = False
+
     def __init__(self, pctx: NekContext, adv: AdvectionDiffusion, omega: float, tol: float = 1e-10, kdim: int = 60,
                  maxiter: int = 20):
-        from .incompressible import refuse_incompressible
+        if not self.projects_stages:
+            from .incompressible import refuse_incompressible
 
-        refuse_incompressible(type(self).__name__, adv)
+            refuse_incompressible(type(self).__name__, adv)
         self._check_model(adv)
         base = adv.ctx.layout
         if not isinstance(pctx.layout, PairLayout) or pctx.layout != pair_layout(base):
@@ -250,4 +257,100 @@ class CoupledResolventOperator(ResolventOperator):
         average_segments(self.adv.face_average, self._avg_ptrs)
 
 
-__all__ = ["CoupledResolventOperator", "ResolventOperator", "pair_context"]
+class IncompressibleResolventOperator(CoupledResolventOperator):
+    """The resolvent of the incompressible linearised Navier-Stokes operator about a base state ``B`` (nekStab's
+    ``resolvent_op``, which integrates exactly this operator), on complex pair vectors:
+
+        matvec:   y = (i omega - P L_B)^-1 P Pi x   on range(P Pi)
+        rmatvec:  y = (-i omega - P L_B†)^-1 P Pi x
+
+    with ``P`` the divergence-free projection of ``lns.projector`` (:mod:`~nekstab_next_amd.pressure`) and ``L_B``,
+    ``L_B†`` of :class:`~nekstab_next_amd.incompressible.LinearisedNavierStokes`.  The rotating-frame Horner stepper
+    and the inner GMRES on ``I - Phi`` are the parents'; a Horner pass is
+
+        nkv_linconv_crhs, the dsavg batch            r   (both halves)
+        nkv_advdiff_cstage, v = NULL, omega = 0       k = minv r
+        lns.projector.project_pair_ptr                k_vel <- P k_vel on the re and the im half: ONE two-system CG
+        nkv_advdiff_cstage, the mask for minv         w = y + c (k + omega-coupling + f)
+
+    as ``LinearisedNavierStokes._propagate`` closes its stages; scalar rows (``n_wf > ldim``) pass unprojected.
+    ``project`` gives ``P Pi f`` on both halves.
+
+    Exactness: ``range(P Pi)`` (on both halves) is invariant under the stage, since ``P k``, the coupling term
+    ``omega s`` of a source in the range and the projected forcing all lie in it.  On it the step is
+    ``y+ = p(dt G) y + dt phi(dt G) f`` with ``G = P L_B - i omega`` restricted to the range, so the module
+    docstring's argument (``p(z) - 1 = z phi(z)``) carries over: the fixed point of ``(I - Phi) y = b`` is
+    ``(i omega - P L_B)^-1 P Pi f`` exactly, for any stable ``dt`` and any ``nsteps``.  ``P`` is self-adjoint in the
+    ``bm1`` inner product, so the adjoint of ``P L_B`` restricted to the range is ``P L_B†`` restricted to it, and
+    ``rmatvec`` is the adjoint of ``matvec`` in the pair inner product up to the CG tolerance of the
+    projector and the tolerance of the inner GMRES, not up to a time-discretisation error.
+
+    ``batched=False`` projects the halves one after the other with ``project_ptr`` (through a staging buffer on
+    the base layout's stride): the path the tests and tools/bench_incompressible_resolvent.py compare with; on
+    one rank it gives the same bits.  ``pair_context(lns)`` builds ``pctx``; ``lns.set_base(q)`` takes effect on
+    the next product.  Anything that is not a ``LinearisedNavierStokes`` is refused."""
+
+    projects_stages = True
+
+    def __init__(self, pctx: NekContext, lns, omega: float, tol: float = 1e-10, kdim: int = 60, maxiter: int = 20,
+                 batched: bool = True):
+        super().__init__(pctx, lns, omega, tol=tol, kdim=kdim, maxiter=maxiter)
+        base = lns.ctx.layout
+        self.lns, self.projector, self.batched = lns, lns.projector, bool(batched)
+        f64 = dict(dtype=torch.float64, device=pctx.device)
+        self._k = torch.zeros(pctx.layout.n_wf * pctx.layout.sv + 2, **f64)
+        self._stage_buf = None if self.batched else torch.zeros(base.ldim * base.sv + 2, **f64)
+        self._bound = self._bound + (lns.mask,)
+
+    @staticmethod
+    def _check_model(adv) -> None:
+        from .incompressible import LinearisedNavierStokes
+
+        if not isinstance(adv, LinearisedNavierStokes):
+            raise ValueError(f"IncompressibleResolventOperator: needs a LinearisedNavierStokes (the base state and the "
+                             f"divergence-free projection), not a {type(adv).__name__}; CoupledResolventOperator is the "
+                             f"resolvent of a LinearisedConvection, ResolventOperator of a plain AdvectionDiffusion")
+
+    def _project_velocity(self, ptr: int, t: torch.Tensor) -> None:
+        """``P`` in place on the velocity rows of both halves of the pair fields at ``ptr`` (the storage ``t``)."""
+        psv = self.ctx.layout.sv
+        if self.batched:
+            self.projector.project_pair_ptr(ptr, ptr + self._half, psv)
+            return
+        base = self.adv.ctx.layout
+        d, n, sv = base.ldim, base.n_v, base.sv
+        off = (ptr - t.data_ptr()) // 8
+        rows = t[off: off + d * psv].view(d, psv)
+        buf = self._stage_buf[: d * sv].view(d, sv)
+        for h in range(2):
+            buf[:, :n].copy_(rows[:, h * n: (h + 1) * n])
+            self.projector.project_ptr(self._stage_buf.data_ptr())
+            rows[:, h * n: (h + 1) * n].copy_(buf[:, :n])
+
+    def _pass(self, y: int, src: int, f, om: float, c: float, out: int, adjoint: bool, zero_rest: bool = False) -> None:
+        """One Horner pass: ``out = y + c (P(minv dsavg r(src)) + om-coupling of src [+ f])``."""
+        rp, kp, st = self._r.data_ptr(), self._k.data_ptr(), self.ctx.stream
+        self._local_rhs(src, adjoint, st)
+        self._cstage(None, self.adv._minv, rp, rp, None, 0.0, 1.0, kp, st)             # k = minv r
+        self._project_velocity(kp, self._k)
+        self._cstage(y, self.lns.mask, kp, src, f, om, c, out, st, zero_rest=zero_rest)
+
+    def _steps(self, y: NekVector, f, adjoint: bool) -> None:
+        """nsteps RK4 steps of dy/dt = (P L_B - i omega) y [+ f] in place (L_B†, +i omega if ``adjoint``)."""
+        om = -self.omega if adjoint else self.omega
+        wa, wb = self._wa.data_ptr(), self._wb.data_ptr()
+        for _ in range(self.nsteps):
+            src = y.ptr
+            for s, out in ((4, wa), (3, wb), (2, wa)):   # w is never its own source: two work vectors in turn
+                self._pass(y.ptr, src, f, om, self.dt / s, out, adjoint)
+                src = out
+            self._pass(y.ptr, src, f, om, self.dt, y.ptr, adjoint, zero_rest=True)
+
+    def project(self, f: NekVector, y: NekVector | None = None) -> NekVector:
+        """``y = P Pi f`` on both halves (in place when ``y`` is None); pressure and time of ``y`` are zeroed."""
+        y = super().project(f, y)
+        self._project_velocity(y.ptr, y.storage)
+        return y
+
+
+__all__ = ["CoupledResolventOperator", "IncompressibleResolventOperator", "ResolventOperator", "pair_context"]
