@@ -1022,6 +1022,40 @@ int nkv_pressure_cg_update2(int64_t n, double* x0, double* x1, double* r0, doubl
                             const double* Ep0, const double* Ep1, const double* red, int Br, const double* rr_old, int Bo,
                             double inv_n, int closed, int init, double* rr_out, int active, void* stream);
 
+/* ---- the fast-diagonalisation preconditioner of that CG -------------------------------------------------
+ * M = blockdiag(M_e), M_e = (S x .. x S) diag( 1 / sum_d c[e][d] lambda_{i_d} ) (S^T x .. x S^T) on the lx2^ldim
+ * pressure values of element e (i_1 along the first, fastest direction): the exact inverse of a separable model of
+ * the element's block of E.  S (lx2 x lx2, row-major, S^T B^ S = I) and lambda (lx2) are the generalised eigenpairs
+ * of the 1-D reference problem and c (nel x ldim, row-major) the element scales; pressure.py documents and builds
+ * them.  Whole elements per workgroup, sum factorisation through LDS; the pressure mesh only, no dsavg, no atomics,
+ * no contraction; any element sub-range (r, z, c offset, nel shortened) gives the bits of the whole.  lx1 = 3 .. 10.
+ *
+ * nkv_pressure_precond:  z = M r over nel elements; z may not meet r.  With partials given workgroup b also writes
+ *   its share of r.z to partials[b] and of sum z to partials[NKV_PRESSURE_PARTIALS + b] (a fixed count of at most
+ *   NKV_PRESSURE_PARTIALS workgroups for a given nel; other slots are not touched).  nel = 0 touches nothing.
+ * nkv_pressure_precond2: the same for two systems (conventions of the two-system entries above: active, the bits
+ *   of the single-system entry, overlapping spans refused); r_s.z_s goes to partials + s NKV_PRESSURE_PARTIALS and
+ *   sum z_s to partials + (2 + s) NKV_PRESSURE_PARTIALS.
+ * nkv_pressure_pgradt / nkv_pressure_pgradt2: nkv_pressure_gradt / nkv_pressure_gradt2 for the preconditioned
+ *   iteration: res (= M r) loses its mean on the load, p <- first ? res - zeta : (res - zeta) + beta p with
+ *   zeta = inv_n times the sum of the B values at zsum (system s: at zsum + s*B); zsum NULL: no shift, the bits of
+ *   the plain entry.  beta as there, from r.z where the plain iteration has r.r.
+ * The preconditioned iteration is four launches and one dsavg batch: pgradt, div, cg_update (rr_old = the
+ * partials of r.z: alpha = r.z / p.(Z E p); it emits r.r for the stop rule), precond. */
+int nkv_pressure_precond(int64_t nel, int lx1, int ldim, const double* S, const double* lambda, const double* c,
+                         const double* r, double* z, double* partials, void* stream);
+int nkv_pressure_precond2(int64_t nel, int lx1, int ldim, const double* S, const double* lambda, const double* c,
+                          const double* r0, const double* r1, double* z0, double* z1, double* partials, int active,
+                          void* stream);
+int nkv_pressure_pgradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                        const double* xm, const double* ym, const double* zm, double* p, const double* res,
+                        const double* rr_new, const double* rr_old, const double* zsum, int B, double inv_n, int first,
+                        double* t, int64_t t_stride, void* stream);
+int nkv_pressure_pgradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                         const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
+                         const double* res1, const double* rr_new, const double* rr_old, const double* zsum, int B,
+                         double inv_n, int first, double* t0, double* t1, int64_t t_stride, int active, void* stream);
+
 /* ---- shard-independent synthetic data ----------------------------------------------------
  * x[row] = 2*u - 1, u = hash(seed, field, global point) in [0,1) with 53 exact bits, for live
  * rows; padding rows = 0; time = 0.  Global point of local point i in a weighted field is

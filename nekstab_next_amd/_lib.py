@@ -192,6 +192,12 @@ _SIGNATURES = {
                                     _P, c_int64, c_int, _P]),
     "nkv_pressure_cg_update2": (c_int, [c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_double, c_int,
                                         c_int, _P, c_int, _P]),
+    "nkv_pressure_precond": (c_int, [c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "nkv_pressure_precond2": (c_int, [c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "nkv_pressure_pgradt": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_double, c_int,
+                                    _P, c_int64, _P]),
+    "nkv_pressure_pgradt2": (c_int, [_L, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
+                                     c_double, c_int, _P, _P, c_int64, c_int, _P]),
 }
 
 # Every symbol include/nekkrylov.h declares (tests check the .so exports all of them).

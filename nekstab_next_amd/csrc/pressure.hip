@@ -22,6 +22,17 @@
 // k_pressure_div2, k_pressure_gradt2 and k_pressure_cg_update2 run that iteration for two systems on one mesh (the
 // re and the im half of a pair vector: the projection inside a stage of the incompressible resolvent) in one launch
 // each, with the bits of the single-system kernels for either system; they stand behind the kernels above.
+// k_pressure_precond applies the fast-diagonalisation preconditioner M of pressure.py (its comment below), and the
+// preconditioned iteration  z = Z M r,  p = z + (r.z / r.z_prev) p,  alpha = r.z / p.(Z E p)  is four launches:
+//   k_pressure_gradt      with zsum: p = (z - zeta) + beta p on its load, zeta = sum z / n, beta from the partials of r.z
+//   k_pressure_div        as above
+//   k_pressure_cg_update  as above, given the partials of r.z for those of r.r; it emits r.r for the stop rule
+//   k_pressure_precond    z = M r; partials of r.z and sum z
+// The apply is its own kernel behind the update, not a rider in an element-tiled update: the update keeps its
+// streaming rate and its bits, the apply also serves DivergenceFreeProjector.precondition, and what riding would
+// save is the second read of r.  Per iteration, in doubles (n GLL points, m pressure values, ldim = 3):
+// gradt 6 n + 3 m, div 7 n + 2 m, update 6 m, precond 2 m: 13 n + 13 m against 13 n + 11 m unpreconditioned
+// (1.672 GB against 1.596 GB at lx1 = 8, E = 22,088), plus the dsavg batch either way.
 #include "nkv_internal.h"
 
 namespace {
@@ -237,7 +248,7 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
     int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
     const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm, double* pin,
     const double* __restrict__ res, const double* __restrict__ rr_new, const double* __restrict__ rr_old, int B,
-    int first, double* __restrict__ t, int64_t t_stride) {
+    int first, double* __restrict__ t, int64_t t_stride, const double* __restrict__ zsum, double inv_n) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
     constexpr int pts = tile_pts<LDIM, NX>();
@@ -257,6 +268,8 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
         const double num = cg_scalar(rr_new, B, h.red), den = cg_scalar(rr_old, B, h.red + 1);
         beta = den != 0.0 ? num / den : 0.0;
     }
+    // the preconditioned iteration: res is M r, whose mean leaves here (zeta = sum z / n; uniform over the grid)
+    const double zeta = res && zsum ? cg_scalar(zsum, B, h.red + 2) * inv_n : 0.0;
     const TilePoint<LDIM, NX> q(h.D, tid, nt);
     const int le = tid / pts, rr = tid - le * pts;
     const int eb = le * pts;
@@ -277,7 +290,9 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt(
                 const int64_t pp = (e0 + le) * ppts + rr;
                 double v;
                 if (res) {
-                    v = first ? res[pp] : res[pp] + beta * pin[pp];
+                    double rv = res[pp];
+                    if (zsum) rv = rv - zeta;
+                    v = first ? rv : rv + beta * pin[pp];
                     pin[pp] = v;
                 } else {
                     v = pin[pp];
@@ -527,7 +542,7 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt2(
     int64_t nel, int epb, const double* __restrict__ Dg, const double* __restrict__ Ig, const double* __restrict__ gwg,
     const double* __restrict__ xm, const double* __restrict__ ym, const double* __restrict__ zm, double* p0, double* p1,
     const double* res0, const double* res1, const double* __restrict__ rr_new, const double* __restrict__ rr_old, int B,
-    int first, double* t0, double* t1, int64_t t_stride, int active) {
+    int first, double* t0, double* t1, int64_t t_stride, int active, const double* __restrict__ zsum, double inv_n) {
 #pragma clang fp contract(off)
     extern __shared__ double lds[];
     constexpr int pts = tile_pts<LDIM, NX>();
@@ -554,6 +569,14 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt2(
             const double num = cg_scalar(rr_new + (int64_t)s * B, B, h.red + 2 * s);
             const double den = cg_scalar(rr_old + (int64_t)s * B, B, h.red + 2 * s + 1);
             beta[s] = den != 0.0 ? num / den : 0.0;
+        }
+    }
+    double zeta[2] = {0.0, 0.0};   // the preconditioned iteration: the mean of M r_s (uniform over the grid)
+    if (with_res && zsum) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (!(active >> s & 1)) continue;
+            zeta[s] = cg_scalar(zsum + (int64_t)s * B, B, h.red + 4 + s) * inv_n;
         }
     }
     const TilePoint<LDIM, NX> q(h.D, tid, nt);
@@ -584,7 +607,9 @@ __global__ __launch_bounds__((tile_threads<LDIM, NX>())) void k_pressure_gradt2(
                 const int64_t pp = (e0 + le) * ppts + rr;
                 double v;
                 if (with_res) {
-                    v = first ? ress[s][pp] : ress[s][pp] + beta[s] * pins[s][pp];
+                    double rv = ress[s][pp];
+                    if (zsum) rv = rv - zeta[s];
+                    v = first ? rv : rv + beta[s] * pins[s][pp];
                     pins[s][pp] = v;
                 } else {
                     v = pins[s][pp];
@@ -705,7 +730,7 @@ void launch_div(int64_t nel, const double* D, const double* I, const double* gw,
 template <int LDIM, int NX>
 void launch_gradt(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
                   const double* zm, double* p, const double* res, const double* rr_new, const double* rr_old, int B,
-                  int first, double* t, int64_t t_stride, hipStream_t st) {
+                  int first, double* t, int64_t t_stride, const double* zsum, double inv_n, hipStream_t st) {
     constexpr int pts = tile_pts<LDIM, NX>();
     const int epb = tile_epb(pts);
     const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)(LDIM + 2) * epb * pts);
@@ -713,7 +738,7 @@ void launch_gradt(int64_t nel, const double* D, const double* I, const double* g
     const int64_t groups = (nel + epb - 1) / epb;
     const int grid = (int)std::min<int64_t>(groups, 4 * kPB);
     hipLaunchKernelGGL((k_pressure_gradt<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
-                       gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride);
+                       gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, zsum, inv_n);
 }
 
 // The two-system launches: the grids, the block sizes and the LDS of launch_div and launch_gradt.
@@ -734,14 +759,178 @@ template <int LDIM, int NX>
 void launch_gradt2(int64_t nel, const double* D, const double* I, const double* gw, const double* xm, const double* ym,
                    const double* zm, double* p0, double* p1, const double* res0, const double* res1, const double* rr_new,
                    const double* rr_old, int B, int first, double* t0, double* t1, int64_t t_stride, int active,
-                   hipStream_t st) {
+                   const double* zsum, double inv_n, hipStream_t st) {
     constexpr int pts = tile_pts<LDIM, NX>();
     const int epb = tile_epb(pts);
     const size_t lds = sizeof(double) * ((size_t)head_doubles<NX>() + (size_t)(LDIM + 2) * epb * pts);
     const int64_t groups = (nel + epb - 1) / epb;
     const int grid = (int)std::min<int64_t>(groups, 4 * kPB);
     hipLaunchKernelGGL((k_pressure_gradt2<LDIM, NX>), dim3(grid), dim3(tile_threads<LDIM, NX>()), lds, st, nel, epb, D, I,
-                       gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0, t1, t_stride, active);
+                       gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0, t1, t_stride, active, zsum, inv_n);
+}
+
+// ------------------------------------------------------------------------------------------
+// The fast-diagonalisation preconditioner: z_e = M_e r_e on the pressure mesh,
+//   M_e = (S x .. x S) diag( 1 / sum_d c[e][d] lambda_{i_d} ) (S^T x .. x S^T),     i_1 along r
+// with S (M x M, row-major; S^T B^ S = I) and lambda the generalised eigenpairs of the 1-D reference problem and
+// c[e][d] the ldim scalars of element e (pressure.py builds all three).  It touches the pressure mesh only: whole
+// elements per workgroup (256 / M^ldim of them when that is more than one), one pressure point per thread.
+// S^T along r, s[, t] by sum factorisation, ping-pong between two LDS tiles, the scale in registers, S back along
+// t[, s], r; the last pass stays in registers.  LDS: S twice (as it is and transposed, so that the coefficient a
+// lane reads is always indexed by the lane's own fastest-varying index: consecutive addresses), lambda, and the two
+// tiles with the r rows padded to an odd length MP = M | 1: the r passes read rows (lanes of one row share an
+// address, rows lie MP doubles apart: with 8-byte reads banked per 32-lane half no two rows of a half meet on a
+// bank for M <= 8), the s and t passes read at strides MP and MP M with the lane index a consecutive.
+// NSYS = 2 serves two systems with one staging of S and one set of denominators; per system the arithmetic, its
+// order, the thread-to-point map, the grid and the slots are those of NSYS = 1: the same bits.  With partials
+// given workgroup b writes its share of r_s.z_s to partials[s kPB + b] and of sum z_s to
+// partials[(NSYS + s) kPB + b].  No atomics, no contraction; element-local.
+// ------------------------------------------------------------------------------------------
+template <int LDIM, int NX>
+constexpr int pc_epb() { return pressure_pts<LDIM, NX>() >= 256 ? 1 : 256 / pressure_pts<LDIM, NX>(); }
+template <int LDIM, int NX>
+constexpr int pc_threads() { return (pc_epb<LDIM, NX>() * pressure_pts<LDIM, NX>() + 63) / 64 * 64; }
+template <int LDIM, int NX>
+constexpr int pc_tile() { return ((NX - 2) | 1) * (LDIM == 3 ? (NX - 2) * (NX - 2) : (NX - 2)); }
+template <int LDIM, int NX>
+constexpr int pc_lds_doubles() {
+    return 2 * (NX - 2) * (NX - 2) + (NX - 2) + (NX & 1) + 3 * kMaxWaves + 2 * pc_epb<LDIM, NX>() * pc_tile<LDIM, NX>();
+}
+
+template <int LDIM, int NX, int NSYS>
+__global__ __launch_bounds__((pc_threads<LDIM, NX>())) void k_pressure_precond(
+    int64_t nel, const double* __restrict__ Sg, const double* __restrict__ lamg, const double* __restrict__ cg,
+    const double* r0, const double* r1, double* z0, double* z1, double* __restrict__ partials, int active) {
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    constexpr int M = NX - 2;
+    constexpr int MP = M | 1;
+    constexpr int ppts = pressure_pts<LDIM, NX>();
+    constexpr int TP = pc_tile<LDIM, NX>();
+    constexpr int epb = pc_epb<LDIM, NX>();
+    double* Sf = lds;                 // Sf[k M + a] = S[k][a]: out_a = sum_k S[k][a] v_k   (S^T v)
+    double* Sb = Sf + M * M;          // Sb[k M + a] = S[a][k]: out_a = sum_k S[a][k] v_k   (S v)
+    double* lam = Sb + M * M;
+    double* red = lam + M + (NX & 1);
+    double* T0 = red + 3 * kMaxWaves;
+    double* T1 = T0 + epb * TP;
+    const int tid = threadIdx.x;
+    for (int t = tid; t < M * M; t += blockDim.x) {
+        Sf[t] = Sg[t];
+        Sb[t] = Sg[(t % M) * M + t / M];
+    }
+    for (int t = tid; t < M; t += blockDim.x) lam[t] = lamg[t];
+    const int le = tid / ppts, q = tid - le * ppts;
+    const int a = q % M, b = (q / M) % M, c = LDIM == 3 ? q / (M * M) : 0;
+    const bool intile = le < epb;
+    const int base = le * TP;
+    const int own = base + a + MP * (b + M * c);
+    const double* const rs[2] = {r0, r1};
+    double* const zs[2] = {z0, z1};
+    double s_rz[NSYS], s_z[NSYS];
+#pragma unroll
+    for (int s = 0; s < NSYS; ++s) s_rz[s] = s_z[s] = 0.0;
+    for (int64_t e0 = (int64_t)blockIdx.x * epb; e0 < nel; e0 += (int64_t)gridDim.x * epb) {
+        const bool live = intile && e0 + le < nel;
+        const int64_t pp = (e0 + le) * ppts + q;
+        __syncthreads();   // S and lambda are staged (first pass); the last pass of the group before has read T1
+        double inv = 0.0;  // lanes without an element carry zeros through the passes
+        if (live) {
+            const double* ce = cg + (e0 + le) * LDIM;
+            double den = ce[0] * lam[a] + ce[1] * lam[b];
+            if constexpr (LDIM == 3) den = den + ce[2] * lam[c];
+            inv = 1.0 / den;
+        }
+#pragma unroll
+        for (int s = 0; s < NSYS; ++s) {
+            if (!(active >> s & 1)) continue;   // (uniform over the grid)
+            // (every pass below ends in a barrier before the tile it read is written again: T0 is free here)
+            const double rv = live ? rs[s][pp] : 0.0;
+            double v = 0.0;
+            if (intile) T0[own] = rv;
+            __syncthreads();
+            if (intile) {      // S^T along r: T0(k, b, c) -> T1(a, b, c)
+                const double* src = T0 + own - a;
+                v = Sf[a] * src[0];
+#pragma unroll
+                for (int k = 1; k < M; ++k) v = v + Sf[k * M + a] * src[k];
+                T1[own] = v;
+            }
+            __syncthreads();
+            if (intile) {      // S^T along s: T1(a, k, c) -> (a, b, c)
+                const double* src = T1 + base + a + MP * M * c;
+                v = Sf[b] * src[0];
+#pragma unroll
+                for (int k = 1; k < M; ++k) v = v + Sf[k * M + b] * src[MP * k];
+            }
+            if constexpr (LDIM == 3) {
+                if (intile) T0[own] = v;
+                __syncthreads();
+                if (intile) {  // S^T along t: T0(a, b, k) -> (a, b, c)
+                    const double* src = T0 + base + a + MP * b;
+                    v = Sf[c] * src[0];
+#pragma unroll
+                    for (int k = 1; k < M; ++k) v = v + Sf[k * M + c] * src[MP * M * k];
+                }
+                v = v * inv;
+                if (intile) T1[own] = v;
+                __syncthreads();
+                if (intile) {  // S along t: T1(a, b, k) -> T0(a, b, c)
+                    const double* src = T1 + base + a + MP * b;
+                    v = Sb[c] * src[0];
+#pragma unroll
+                    for (int k = 1; k < M; ++k) v = v + Sb[k * M + c] * src[MP * M * k];
+                }
+            } else {
+                v = v * inv;
+            }
+            if (intile) T0[own] = v;
+            __syncthreads();
+            if (intile) {      // S along s: T0(a, k, c) -> T1(a, b, c)
+                const double* src = T0 + base + a + MP * M * c;
+                v = Sb[b] * src[0];
+#pragma unroll
+                for (int k = 1; k < M; ++k) v = v + Sb[k * M + b] * src[MP * k];
+                T1[own] = v;
+            }
+            __syncthreads();
+            if (intile) {      // S along r: T1(k, b, c) -> the point (a, b, c)
+                const double* src = T1 + own - a;
+                v = Sb[a] * src[0];
+#pragma unroll
+                for (int k = 1; k < M; ++k) v = v + Sb[k * M + a] * src[k];
+            }
+            if (live) {
+                zs[s][pp] = v;
+                s_rz[s] += rv * v;
+                s_z[s] += v;
+            }
+        }
+    }
+    if (partials) {
+#pragma unroll
+        for (int s = 0; s < NSYS; ++s) {
+            if (!(active >> s & 1)) continue;
+            double unused = 0.0;
+            block_sum3(s_rz[s], s_z[s], unused, red);
+            if (tid == 0) {
+                partials[(int64_t)s * kPB + blockIdx.x] = s_rz[s];
+                partials[(int64_t)(NSYS + s) * kPB + blockIdx.x] = s_z[s];
+            }
+        }
+    }
+}
+
+template <int LDIM, int NX, int NSYS>
+void launch_precond(int64_t nel, const double* S_, const double* lam, const double* c, const double* r0, const double* r1,
+                    double* z0, double* z1, double* partials, int active, hipStream_t st) {
+    constexpr int epb = pc_epb<LDIM, NX>();
+    static_assert(pc_threads<LDIM, NX>() <= 64 * kMaxWaves, "block_sum3 holds kMaxWaves waves");
+    const size_t lds = sizeof(double) * (size_t)pc_lds_doubles<LDIM, NX>();
+    const int64_t groups = (nel + epb - 1) / epb;
+    const int grid = (int)std::min<int64_t>(groups, kPB);
+    hipLaunchKernelGGL((k_pressure_precond<LDIM, NX, NSYS>), dim3(grid), dim3(pc_threads<LDIM, NX>()), lds, st, nel, S_, lam,
+                       c, r0, r1, z0, z1, partials, active);
 }
 
 // The spans a two-system entry writes and reads (NULL operands are left out): no written span may meet another
@@ -825,11 +1014,12 @@ int nkv_pressure_div(const nkv_layout* L, int lx1, int ldim, const double* D, co
     return NKV_OK;
 }
 
-int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
-                       const double* xm, const double* ym, const double* zm, double* p, const double* res,
-                       const double* rr_new, const double* rr_old, int B, int first, double* t, int64_t t_stride,
-                       void* stream) {
-    static const char who[] = "pressure_gradt";
+// nkv_pressure_gradt and nkv_pressure_pgradt: the second with zsum (the B partials of sum M r; NULL: no shift).
+static int pressure_gradt_entry(const char* who, const nkv_layout* L, int lx1, int ldim, const double* D,
+                                const double* interp, const double* gw, const double* xm, const double* ym,
+                                const double* zm, double* p, const double* res, const double* rr_new,
+                                const double* rr_old, int B, int first, double* t, int64_t t_stride, const double* zsum,
+                                double inv_n, void* stream) {
     CHECK(check_layout(L));
     if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
     CHECK(check_pressure_args(who, L, lx1, ldim, zm));
@@ -847,6 +1037,11 @@ int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, 
         CHECK(need(rr_old, who, "rr_old"));
         if (B < 1 || B > kPB) return fail(NKV_EINVAL, "%s: B=%d outside 1..%d", who, B, kPB);
     }
+    if (zsum) {
+        CHECK(need(res, who, "res (zsum shifts res)"));
+        if (B < 1 || B > kPB) return fail(NKV_EINVAL, "%s: B=%d outside 1..%d", who, B, kPB);
+        if (!std::isfinite(inv_n)) return fail(NKV_EINVAL, "%s: inv_n=%g", who, inv_n);
+    }
     if (res == p) return fail(NKV_EINVAL, "%s: res is p", who);
     const int pts = ldim == 3 ? lx1 * lx1 * lx1 : lx1 * lx1;
     const int64_t nel = L->n_v / pts;
@@ -854,14 +1049,32 @@ int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, 
 #define NKV_PR_GT(NX)                                                                                                 \
     case NX:                                                                                                          \
         if (ldim == 3)                                                                                                \
-            launch_gradt<3, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, st);   \
+            launch_gradt<3, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, zsum,  \
+                                inv_n, st);                                                                           \
         else                                                                                                          \
-            launch_gradt<2, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, st);   \
+            launch_gradt<2, NX>(nel, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B, first, t, t_stride, zsum,  \
+                                inv_n, st);                                                                           \
         break;
     switch (lx1) { NKV_PR_CASES(NKV_PR_GT) }
 #undef NKV_PR_GT
     NKV_LAUNCHED();
     return NKV_OK;
+}
+
+int nkv_pressure_gradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                       const double* xm, const double* ym, const double* zm, double* p, const double* res,
+                       const double* rr_new, const double* rr_old, int B, int first, double* t, int64_t t_stride,
+                       void* stream) {
+    return pressure_gradt_entry("pressure_gradt", L, lx1, ldim, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B,
+                                first, t, t_stride, nullptr, 0.0, stream);
+}
+
+int nkv_pressure_pgradt(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                        const double* xm, const double* ym, const double* zm, double* p, const double* res,
+                        const double* rr_new, const double* rr_old, const double* zsum, int B, double inv_n, int first,
+                        double* t, int64_t t_stride, void* stream) {
+    return pressure_gradt_entry("pressure_pgradt", L, lx1, ldim, D, interp, gw, xm, ym, zm, p, res, rr_new, rr_old, B,
+                                first, t, t_stride, zsum, inv_n, stream);
 }
 
 int nkv_pressure_cg_update(int64_t n, double* x, double* r, const double* p, const double* Ep, const double* red, int Br,
@@ -947,11 +1160,12 @@ int nkv_pressure_div2(const nkv_layout* L, int lx1, int ldim, const double* D, c
     return NKV_OK;
 }
 
-int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
-                        const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
-                        const double* res1, const double* rr_new, const double* rr_old, int B, int first, double* t0,
-                        double* t1, int64_t t_stride, int active, void* stream) {
-    static const char who[] = "pressure_gradt2";
+// nkv_pressure_gradt2 and nkv_pressure_pgradt2: the second with zsum (system s at zsum + s*B; NULL: no shift).
+static int pressure_gradt2_entry(const char* who, const nkv_layout* L, int lx1, int ldim, const double* D,
+                                 const double* interp, const double* gw, const double* xm, const double* ym,
+                                 const double* zm, double* p0, double* p1, const double* res0, const double* res1,
+                                 const double* rr_new, const double* rr_old, int B, int first, double* t0, double* t1,
+                                 int64_t t_stride, int active, const double* zsum, double inv_n, void* stream) {
     CHECK(check_layout(L));
     if (L->n_v == 0) return NKV_OK;   // an empty shard: nothing to touch
     CHECK(check_pressure_args(who, L, lx1, ldim, zm));
@@ -995,6 +1209,12 @@ int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D,
         sp.reads(rr_new, 2 * (int64_t)B, "rr_new");
         sp.reads(rr_old, 2 * (int64_t)B, "rr_old");
     }
+    if (zsum) {
+        if (!with_res) return fail(NKV_EINVAL, "%s: zsum shifts res0 / res1, which are NULL", who);
+        if (B < 1 || B > kPB) return fail(NKV_EINVAL, "%s: B=%d outside 1..%d", who, B, kPB);
+        if (!std::isfinite(inv_n)) return fail(NKV_EINVAL, "%s: inv_n=%g", who, inv_n);
+        sp.reads(zsum, 2 * (int64_t)B, "zsum");
+    }
     CHECK(sp.check(who));
     if (!(active & 1)) res0 = nullptr;   // the kernel takes the res path when either is given
     if (!(active & 2)) res1 = nullptr;
@@ -1003,15 +1223,31 @@ int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D,
     case NX:                                                                                                         \
         if (ldim == 3)                                                                                               \
             launch_gradt2<3, NX>(nel, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0,   \
-                                 t1, t_stride, active, st);                                                          \
+                                 t1, t_stride, active, zsum, inv_n, st);                                             \
         else                                                                                                         \
             launch_gradt2<2, NX>(nel, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new, rr_old, B, first, t0,   \
-                                 t1, t_stride, active, st);                                                          \
+                                 t1, t_stride, active, zsum, inv_n, st);                                             \
         break;
     switch (lx1) { NKV_PR_CASES(NKV_PR_GT2) }
 #undef NKV_PR_GT2
     NKV_LAUNCHED();
     return NKV_OK;
+}
+
+int nkv_pressure_gradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                        const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
+                        const double* res1, const double* rr_new, const double* rr_old, int B, int first, double* t0,
+                        double* t1, int64_t t_stride, int active, void* stream) {
+    return pressure_gradt2_entry("pressure_gradt2", L, lx1, ldim, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new,
+                                 rr_old, B, first, t0, t1, t_stride, active, nullptr, 0.0, stream);
+}
+
+int nkv_pressure_pgradt2(const nkv_layout* L, int lx1, int ldim, const double* D, const double* interp, const double* gw,
+                         const double* xm, const double* ym, const double* zm, double* p0, double* p1, const double* res0,
+                         const double* res1, const double* rr_new, const double* rr_old, const double* zsum, int B,
+                         double inv_n, int first, double* t0, double* t1, int64_t t_stride, int active, void* stream) {
+    return pressure_gradt2_entry("pressure_pgradt2", L, lx1, ldim, D, interp, gw, xm, ym, zm, p0, p1, res0, res1, rr_new,
+                                 rr_old, B, first, t0, t1, t_stride, active, zsum, inv_n, stream);
 }
 
 int nkv_pressure_cg_update2(int64_t n, double* x0, double* x1, double* r0, double* r1, const double* p0, const double* p1,
@@ -1059,6 +1295,81 @@ int nkv_pressure_cg_update2(int64_t n, double* x0, double* x1, double* r0, doubl
     const int grid = grid_for(n, kPB);
     hipLaunchKernelGGL(k_pressure_cg_update2, dim3(grid), dim3(kThreads), 0, S(stream), n, x0, x1, r0, r1, p0, p1, Ep0, Ep1,
                        red, Br, rr_old, Bo, inv_n, closed, init, rr_out, active);
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+static int check_precond_args(const char* who, int64_t nel, int lx1, int ldim, const double* S_, const double* lam,
+                              const double* c) {
+    if (nel < 0) return fail(NKV_EINVAL, "%s: nel=%lld", who, (long long)nel);
+    if (ldim != 2 && ldim != 3) return fail(NKV_EINVAL, "%s: ldim=%d (2 or 3)", who, ldim);
+    if (lx1 < 3 || lx1 > 10) return fail(NKV_EINVAL, "%s: lx1=%d outside 3..10", who, lx1);
+    CHECK(need(S_, who, "S"));
+    CHECK(need(lam, who, "lambda"));
+    CHECK(need(c, who, "c"));
+    return NKV_OK;
+}
+
+int nkv_pressure_precond(int64_t nel, int lx1, int ldim, const double* S_, const double* lam, const double* c,
+                         const double* r, double* z, double* partials, void* stream) {
+    static const char who[] = "pressure_precond";
+    CHECK(check_precond_args(who, nel, lx1, ldim, S_, lam, c));
+    if (nel == 0) return NKV_OK;   // an empty shard: nothing to touch (its partial slots stay as they are)
+    CHECK(need(r, who, "r"));
+    CHECK(need(z, who, "z"));
+    const int m = lx1 - 2;
+    const int64_t npz = nel * (ldim == 3 ? m * m * m : m * m);
+    Spans sp;
+    sp.reads(r, npz, "r");
+    sp.writes(z, npz, "z");
+    if (partials) sp.writes(partials, 2 * (int64_t)kPB, "partials");
+    CHECK(sp.check(who));
+    hipStream_t st = S(stream);
+#define NKV_PR_PC(NX)                                                                                    \
+    case NX:                                                                                             \
+        if (ldim == 3) launch_precond<3, NX, 1>(nel, S_, lam, c, r, nullptr, z, nullptr, partials, 1, st); \
+        else launch_precond<2, NX, 1>(nel, S_, lam, c, r, nullptr, z, nullptr, partials, 1, st);         \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_PC) }
+#undef NKV_PR_PC
+    NKV_LAUNCHED();
+    return NKV_OK;
+}
+
+int nkv_pressure_precond2(int64_t nel, int lx1, int ldim, const double* S_, const double* lam, const double* c,
+                          const double* r0, const double* r1, double* z0, double* z1, double* partials, int active,
+                          void* stream) {
+    static const char who[] = "pressure_precond2";
+    CHECK(check_precond_args(who, nel, lx1, ldim, S_, lam, c));
+    CHECK(check_active(who, active));
+    if (nel == 0) return NKV_OK;   // an empty shard: nothing to touch (its partial slots stay as they are)
+    const int m = lx1 - 2;
+    const int64_t npz = nel * (ldim == 3 ? m * m * m : m * m);
+    static const char* const rn[2] = {"r0", "r1"};
+    static const char* const zn[2] = {"z0", "z1"};
+    const double* const rs[2] = {r0, r1};
+    double* const zs[2] = {z0, z1};
+    Spans sp;
+    for (int s = 0; s < 2; ++s) {
+        if (!(active >> s & 1)) continue;
+        CHECK(need(rs[s], who, rn[s]));
+        CHECK(need(zs[s], who, zn[s]));
+        sp.reads(rs[s], npz, rn[s]);
+        sp.writes(zs[s], npz, zn[s]);
+        if (partials) {
+            sp.writes(partials + (int64_t)s * kPB, kPB, "partials");
+            sp.writes(partials + (int64_t)(2 + s) * kPB, kPB, "partials");
+        }
+    }
+    CHECK(sp.check(who));
+    hipStream_t st = S(stream);
+#define NKV_PR_PC2(NX)                                                                                   \
+    case NX:                                                                                             \
+        if (ldim == 3) launch_precond<3, NX, 2>(nel, S_, lam, c, r0, r1, z0, z1, partials, active, st);  \
+        else launch_precond<2, NX, 2>(nel, S_, lam, c, r0, r1, z0, z1, partials, active, st);            \
+        break;
+    switch (lx1) { NKV_PR_CASES(NKV_PR_PC2) }
+#undef NKV_PR_PC2
     NKV_LAUNCHED();
     return NKV_OK;
 }

@@ -36,16 +36,16 @@ from .vector import NekContext, NekVector
 class LinearisedNavierStokes(LinearisedConvection):
     """``y = p(dt · P L_B)^nsteps P Π x`` and its adjoint about a base state ``B`` (module docstring):
     :class:`LinearisedConvection` with the divergence-free projection behind every right-hand side.  ``tol``,
-    ``maxiter``, ``check_every``, ``closed``: the projector's (``self.projector``); everything else as in the
-    parent."""
+    ``maxiter``, ``check_every``, ``closed``, ``preconditioner``: the projector's (``self.projector``); everything
+    else as in the parent."""
 
     def __init__(self, ctx: NekContext, coords: dict, base, kappa, dt: float, nsteps: int, mask=None,
                  face_average="auto", tol: float = 1e-12, maxiter: int | None = None, check_every: int = 8,
-                 closed="auto"):
+                 closed="auto", preconditioner=None):
         super().__init__(ctx, coords, base, kappa, dt, nsteps, mask=mask, face_average=face_average)
         lay = ctx.layout
         self.projector = DivergenceFreeProjector(ctx, tol=tol, maxiter=maxiter, check_every=check_every, closed=closed,
-                                                 operator=self)
+                                                 operator=self, preconditioner=preconditioner)
         self._k = torch.zeros(lay.n_wf * lay.sv + 2, dtype=torch.float64, device=ctx.device)
 
     def _projected_rhs(self) -> int:
@@ -83,12 +83,14 @@ class IncompressibleFlow(ViscousBurgers):
     """The incompressible flow ``dq/dt = N(q)`` and its time-``tau`` map ``Φ`` (module docstring):
     :class:`ViscousBurgers` with ``k_i = P(minv · dsavg r(s_i)) + g`` in every stage and ``g`` projected by
     ``P Π`` once.  ``linearized(q)`` returns the :class:`LinearisedNavierStokes` the flow owns.  ``tol``,
-    ``maxiter``, ``check_every``, ``closed``: the projector's (``self.projector``)."""
+    ``maxiter``, ``check_every``, ``closed``, ``preconditioner``: the projector's (``self.projector``), passed on to
+    the linearisation too."""
 
     def __init__(self, ctx: NekContext, coords: dict, kappa, dt: float, nsteps: int, forcing=None, mask=None,
                  face_average="auto", tol: float = 1e-12, maxiter: int | None = None, check_every: int = 8,
-                 closed="auto"):
-        self._projector_args = dict(tol=tol, maxiter=maxiter, check_every=check_every, closed=closed)
+                 closed="auto", preconditioner=None):
+        self._projector_args = dict(tol=tol, maxiter=maxiter, check_every=check_every, closed=closed,
+                                    preconditioner=preconditioner)
         super().__init__(ctx, coords, kappa, dt, nsteps, forcing=forcing, mask=mask, face_average=face_average)
         self.projector = self.lin.projector
 

@@ -32,6 +32,31 @@ stage the coordinates and form the factors once for both, one ``dsavg`` batch of
 all-reduce per reduced quantity.  Every system keeps its own scalars and its own stop; one that has met it is
 frozen (dropped from the ``active`` mask of every later launch), so each result carries the bits and the iteration
 count of ``project_ptr`` on it alone.
+
+``preconditioner="fdm"`` runs the same solve as preconditioned CG with a non-overlapping element-block
+preconditioner applied by fast diagonalisation (the local solve of Nek5000's Schwarz smoother without overlap or
+coarse grid).  For ``n = lx1`` take the GLL weights ``ρ`` and derivative ``D̂``, the ``m = lx1 − 2`` Gauss weights ``w``
+and the interpolation ``I`` (m × n); with ``ρ̃ = ρ``, its two end weights doubled (the mass an interior interface sees
+after assembly), ``D̃ = diag(w) I D̂`` and ``J̃ = diag(w) I``:
+
+    Â = D̃ diag(1/ρ̃) D̃ᵀ,   B̂ = J̃ diag(1/ρ̃) J̃ᵀ,   Â S = B̂ S Λ,   Sᵀ B̂ S = I        (``fdm_eigenpairs``)
+
+Per element ``e`` and local direction ``d``, ``h[e,d]`` is half the distance between the centroids of the two opposite
+faces and ``c[e,d] = (Π_k h[e,k]) / h[e,d]²`` (``fdm_element_scales``).  Then, with ``i_1`` along r,
+
+    M_e = (S ⊗ … ⊗ S) · diag( 1 / Σ_d c[e,d] λ_{i_d} ) · (Sᵀ ⊗ … ⊗ Sᵀ)              (``nkv_pressure_precond``)
+
+is the exact inverse of ``Σ_d c[e,d] (Â in slot d, B̂ elsewhere)`` on an undeformed rectilinear element, and
+``M = blockdiag(M_e)`` is symmetric positive definite and element-local.  The iteration is
+
+    z = Z M r,   p = z + (r·z / r·z_prev) p,   α = r·z / p·(Z E p)
+
+with the stop rule, ``maxiter`` and the errors of the plain iteration (``‖r‖₂ ≤ tol·‖b‖₂`` every ``check_every``
+iterations).  It is four launches: ``nkv_pressure_pgradt`` (``nkv_pressure_gradt`` that also takes the mean off ``z``
+on its load), ``nkv_pressure_div``, ``nkv_pressure_cg_update`` (given the partials of ``r·z`` where the plain
+iteration gives those of ``r·r``; it still emits ``r·r`` for the stop) and ``nkv_pressure_precond``, which emits the
+partials of ``r·z`` and ``Σz``.  The three partial rows share one buffer, so several ranks reduce them in one
+all-reduce.  ``preconditioner=None`` (the default) runs the plain iteration above, unchanged.
 """
 from __future__ import annotations
 
@@ -50,13 +75,47 @@ from .vector import NekContext, NekVector
 CLOSED_RATIO = 1e-6
 
 
+def fdm_eigenpairs(lx1: int):
+    """``(S, lambda)`` of the 1-D reference problem of the fast-diagonalisation preconditioner (module docstring),
+    in f64: ``A^ S = B^ S diag(lambda)``, ``S^T B^ S = I``."""
+    from scipy.linalg import eigh
+
+    from .sensitivity import gll_derivative
+    from .synthetic import gll_weights
+
+    m = lx1 - 2
+    rho = np.array(gll_weights(lx1), dtype=np.float64)
+    rho[0] *= 2.0                                                    # the mass an interior interface sees
+    rho[-1] *= 2.0
+    Jt = np.polynomial.legendre.leggauss(m)[1][:, None] * interp_matrix(gll_points(lx1), gauss_points(m))
+    Dt = Jt @ gll_derivative(lx1)
+    A, B = (Dt / rho) @ Dt.T, (Jt / rho) @ Jt.T
+    lam, S = eigh(0.5 * (A + A.T), 0.5 * (B + B.T))
+    return np.ascontiguousarray(S), lam
+
+
+def fdm_element_scales(xyz, lx1: int, ldim: int) -> np.ndarray:
+    """``c[e, d] = (prod_k h[e, k]) / h[e, d]^2`` (nel x ldim) from the GLL coordinates ``xyz`` (ldim arrays of
+    ``nel·lx1^ldim``): ``h[e, d]`` is half the distance between the centroids of the two faces across ``d``."""
+    X = np.stack([np.asarray(x, dtype=np.float64).reshape(-1, lx1 if ldim == 3 else 1, lx1, lx1) for x in xyz])
+    h = []
+    for d in range(ldim):
+        lo, hi = (np.take(X, i, axis=4 - d) for i in (0, lx1 - 1))     # r is the last axis of (comp, e, k, j, i)
+        lo, hi = (f.reshape(ldim, f.shape[1], -1).mean(axis=2) for f in (lo, hi))
+        h.append(0.5 * np.sqrt(np.sum((hi - lo) ** 2, axis=0)))
+    h = np.stack(h, axis=1)
+    return np.ascontiguousarray(np.prod(h, axis=1, keepdims=True) / h ** 2)
+
+
 class DivergenceFreeProjector:
     """``P`` on the velocity rows (module docstring).
 
     ``coords``, ``mask``, ``face_average``: as for :class:`AdvectionDiffusion`; or pass ``operator=`` (an
     :class:`AdvectionDiffusion` on ``ctx``) to share its mesh, ``minv`` and ``face_average``.  ``tol``: CG stops at
     ``‖r‖ ≤ tol·‖b‖``, tested every ``check_every`` iterations; more than ``maxiter`` iterations (default
-    ``2·npz_global + 20``) raise ``RuntimeError``.  ``closed``: ``"auto"``, True or False.
+    ``2·npz_global + 20``) raise ``RuntimeError``.  ``closed``: ``"auto"``, True or False.  ``preconditioner``: None
+    (plain CG) or ``"fdm"`` (module docstring); with ``"fdm"``, ``precondition(r, out)`` applies ``M`` and ``fdm_S``,
+    ``fdm_lambda``, ``fdm_c`` hold its data on the device.
 
     ``apply(x, y)`` projects the velocity rows of a state vector; ``last_iterations`` is the count of the latest
     solve and ``phi`` its multiplier (this rank's ``nel·lx2^ldim`` values).  ``project_pair_ptr`` projects two
@@ -64,7 +123,8 @@ class DivergenceFreeProjector:
     (``phi`` stays the latest single solve's)."""
 
     def __init__(self, ctx: NekContext, coords: dict | None = None, mask=None, face_average="auto", tol: float = 1e-12,
-                 maxiter: int | None = None, check_every: int = 8, closed="auto", operator: AdvectionDiffusion | None = None):
+                 maxiter: int | None = None, check_every: int = 8, closed="auto", operator: AdvectionDiffusion | None = None,
+                 preconditioner: str | None = None):
         lay = ctx.layout
         if isinstance(lay, PairLayout):
             raise ValueError("DivergenceFreeProjector: a PairLayout context is refused (project the halves of a pair "
@@ -77,6 +137,8 @@ class DivergenceFreeProjector:
                              "maxiter >= 1")
         if closed not in ("auto", True, False):
             raise ValueError("closed: 'auto', True or False")
+        if preconditioner not in (None, "fdm"):
+            raise ValueError(f"preconditioner={preconditioner!r}: None or 'fdm'")
         if operator is None:
             zero = [np.zeros(lay.n_v) for _ in range(lay.ldim)]
             operator = AdvectionDiffusion(ctx, coords, zero, 0.0, 1.0, 1, mask=mask, face_average=face_average)
@@ -110,12 +172,44 @@ class DivergenceFreeProjector:
         self.last_iterations = 0
         self.last_iterations_each = (0, 0)                           # of the latest two-system solve
         self._pair = None                                            # the buffers of project_pair_ptr
+        self.preconditioner = preconditioner
+        self.fdm_S = self.fdm_lambda = self.fdm_c = None
+        if preconditioner == "fdm":
+            self._build_fdm()
         self.closed_ratio = None
         self.closed = False
         if closed == "auto":
             self.closed = self._detect_closed()
         else:
             self.closed = bool(closed)
+
+    # ---- the preconditioner ----
+    def _build_fdm(self) -> None:
+        """``S``, ``lambda`` (the same on every rank) and the scales ``c`` of this rank's elements, on the device;
+        ``z`` and the two partial buffers of the preconditioned iteration: rows r.r, r.z, sum z."""
+        ctx, lay, B = self.ctx, self.ctx.layout, self.PARTIALS
+        f64 = dict(dtype=torch.float64, device=ctx.device)
+        S, lam = fdm_eigenpairs(lay.lx1)
+        c = fdm_element_scales([x[: lay.n_v].cpu().numpy() for x in self.op.xyz], lay.lx1, lay.ldim)
+        self.fdm_S, self.fdm_lambda = torch.as_tensor(S).to(ctx.device), torch.as_tensor(lam).to(ctx.device)
+        self.fdm_c = torch.zeros(max(c.shape[0], 1), lay.ldim, **f64)
+        self.fdm_c[: c.shape[0]] = torch.as_tensor(c).to(ctx.device)
+        self._nel = c.shape[0]
+        self._z = torch.zeros(max(self.npz, 2), **f64)
+        self._pz = [torch.zeros(3 * B, **f64) for _ in range(2)]
+        self._fdm_head = (self._nel, lay.lx1, lay.ldim, self.fdm_S.data_ptr(), self.fdm_lambda.data_ptr(),
+                          self.fdm_c.data_ptr())
+
+    def precondition(self, r: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """``out = M r`` on this rank's pressure values (element-local: no communication, no deflation)."""
+        if self.preconditioner != "fdm":
+            raise RuntimeError("DivergenceFreeProjector.precondition: built with preconditioner=None")
+        for t, name in ((r, "r"), (out, "out")):
+            if t.dtype != torch.float64 or t.device != self._z.device or not t.is_contiguous() or t.numel() < self.npz:
+                raise ValueError(f"precondition: {name} must be a contiguous f64 tensor of at least {self.npz} values "
+                                 "on the projector's device")
+        self.ctx.call_nl("nkv_pressure_precond", *self._fdm_head, r.data_ptr(), out.data_ptr(), None, self.ctx.stream)
+        return out
 
     # ---- the operators ----
     def _gradt(self, p: torch.Tensor, res=None, rr_new=None, rr_old=None, B: int = 1, first: bool = True) -> None:
@@ -182,6 +276,8 @@ class DivergenceFreeProjector:
 
     def project_ptr(self, v_ptr: int, out_ptr: int | None = None) -> None:
         """``P`` on the ``ldim`` segments (stride ``sv``) at ``v_ptr``, into ``out_ptr`` (default: in place)."""
+        if self.preconditioner == "fdm":
+            return self._project_ptr_fdm(v_ptr, out_ptr)
         ctx, lay = self.ctx, self.ctx.layout
         out_ptr = v_ptr if out_ptr is None else out_ptr
         minv = self.op._minv
@@ -221,6 +317,62 @@ class DivergenceFreeProjector:
         ctx.call("nkv_advdiff_stage", v_ptr, lay.sv, minv.data_ptr(), self._t.data_ptr(), lay.sv, -1.0, out_ptr, lay.sv,
                  lay.ldim, 0, ctx.stream)
 
+    def _project_ptr_fdm(self, v_ptr: int, out_ptr: int | None) -> None:
+        """``project_ptr`` by preconditioned CG: ``z = Z M r``, ``p = z + (r.z / r.z_prev) p``, ``alpha = r.z /
+        p.(Z E p)``; the stop rule, ``maxiter`` and the errors of the plain iteration.  Four launches an iteration:
+        ``nkv_pressure_pgradt`` (takes the mean off ``z`` on its load), ``nkv_pressure_div``,
+        ``nkv_pressure_cg_update`` (``r.z`` for ``r.r`` in ``alpha``; it still emits ``r.r``) and
+        ``nkv_pressure_precond``.  The partials of ``r.r``, ``r.z`` and ``sum z`` share one buffer and one
+        all-reduce."""
+        ctx, lay, PB = self.ctx, self.ctx.layout, self.PARTIALS
+        out_ptr = v_ptr if out_ptr is None else out_ptr
+        minv, st = self.op._minv, ctx.stream
+        inv_n, closed = 1.0 / max(self.npz_global, 1), int(self.closed)
+        x, r, p, Ep, z = (a.data_ptr() for a in (self._x, self._r, self._p, self._Ep, self._z))
+
+        def update_precond(red, Br, rz_ptr, Bo, buf, init):
+            ctx.call_nl("nkv_pressure_cg_update", self.npz, x, r, p, Ep, None if red is None else red.data_ptr(), Br,
+                        rz_ptr, Bo, inv_n, closed, int(init), buf.data_ptr(), st)
+            ctx.call_nl("nkv_pressure_precond", *self._fdm_head, r, z, buf.data_ptr() + 8 * PB, st)
+            return self._reduced(buf, 3)                             # rows r.r, r.z, sum z: Bo values each
+
+        # b = Z D v; x = 0, r = b, z = M r
+        self._div(v_ptr, None, self._Ep, pv=self._p)
+        red, Br = self._reduced(self._red, 3)
+        cur, Bo = update_precond(red, Br, None, 1, self._pz[0], True)
+        bb = self._host_sum(cur[:Bo])
+        it = 0
+        if bb > 0.0 and math.isfinite(bb):
+            stop = (self.tol ** 2) * bb
+            prev, done = None, False
+            while not done:
+                if it >= self.maxiter:
+                    self.last_iterations = it
+                    raise RuntimeError(f"DivergenceFreeProjector: CG did not reach tol={self.tol:g} in maxiter={self.maxiter} "
+                                       f"iterations (|r|/|b| = {math.sqrt(max(self._host_sum(cur[:Bo]), 0.0) / bb):.3e})")
+                ctx.call("nkv_pressure_pgradt", *self._head, p, z, cur.data_ptr() + 8 * Bo,
+                         None if prev is None else prev.data_ptr() + 8 * Bo,
+                         cur.data_ptr() + 16 * Bo if closed else None, Bo, inv_n, int(it == 0), self._t.data_ptr(), lay.sv,
+                         st)
+                average_segments(self.op.face_average, self._t_ptrs)
+                self._div(self._t.data_ptr(), minv, self._Ep, pv=self._p)
+                red, Br = self._reduced(self._red, 3)
+                prev = cur
+                cur, Bo = update_precond(red, Br, cur.data_ptr() + 8 * Bo, Bo, self._pz[(it + 1) % 2], False)
+                it += 1
+                if it % self.check_every == 0:
+                    now = self._host_sum(cur[:Bo])
+                    if not math.isfinite(now):
+                        raise RuntimeError("DivergenceFreeProjector: the CG residual is not finite")
+                    done = now <= stop
+        elif not math.isfinite(bb):
+            raise RuntimeError("DivergenceFreeProjector: the divergence of the input is not finite")
+        self.last_iterations = it
+        # out = v - minv dsavg(D^T x)   (x = 0 when b = 0: out = v)
+        self._gradt(self._x)
+        ctx.call("nkv_advdiff_stage", v_ptr, lay.sv, minv.data_ptr(), self._t.data_ptr(), lay.sv, -1.0, out_ptr, lay.sv,
+                 lay.ldim, 0, ctx.stream)
+
     # ---- the solve of two systems at once ----
     def _pair_buffers(self):
         """The second set of CG vectors, allocated on first use: x, r, p, Ep, D^T p and the partial rows of both
@@ -236,6 +388,8 @@ class DivergenceFreeProjector:
             t_ptrs = [t.data_ptr() + 8 * k * lay.sv for k in range(2 * lay.ldim)]
             t_sets = {1: t_ptrs[: lay.ldim], 2: t_ptrs[lay.ldim:], 3: t_ptrs}   # by ``active``
             self._pair = dict(x=x, r=r, p=p, Ep=Ep, t=t, red=red, rr=rr, t_sets=t_sets, chk=torch.zeros(2, **f64))
+            if self.preconditioner == "fdm":     # z, and the rows r.r, r.z, sum z of both systems (system s: row 2q + s)
+                self._pair.update(z=torch.zeros(2, npad, **f64), pz=[torch.zeros(6 * B, **f64) for _ in range(2)])
         return self._pair
 
     def _reduced2(self, part: torch.Tensor, rows: int):
@@ -263,6 +417,8 @@ class DivergenceFreeProjector:
         and stop; one that meets it at a check (or has ``b = 0``) is frozen, its bit cleared from ``active`` for
         every later launch, so each result is bit for bit ``project_ptr``'s for it alone on one rank, with the same
         count (``last_iterations_each``; ``last_iterations`` is their maximum)."""
+        if self.preconditioner == "fdm":
+            return self._project_pair_ptr_fdm(v0_ptr, v1_ptr, stride, out0_ptr, out1_ptr)
         ctx, lay = self.ctx, self.ctx.layout
         out0_ptr = v0_ptr if out0_ptr is None else out0_ptr
         out1_ptr = v1_ptr if out1_ptr is None else out1_ptr
@@ -326,6 +482,75 @@ class DivergenceFreeProjector:
         self.last_iterations_each, self.last_iterations = tuple(its), max(its)
         # out = v - minv dsavg(D^T x)   (x = 0 when b = 0: out = v)
         gradt2(x, (None, None), None, None, 1, True, 3)
+        for v_ptr, t_ptr, o_ptr in ((v0_ptr, tp[0], out0_ptr), (v1_ptr, tp[1], out1_ptr)):
+            ctx.call("nkv_advdiff_stage", v_ptr, stride, minv.data_ptr(), t_ptr, sv, -1.0, o_ptr, stride, d, 0, st)
+
+    def _project_pair_ptr_fdm(self, v0_ptr: int, v1_ptr: int, stride: int, out0_ptr: int | None,
+                              out1_ptr: int | None) -> None:
+        """``project_pair_ptr`` by the preconditioned iteration of ``_project_ptr_fdm`` over the two-system entries
+        (``nkv_pressure_pgradt2``, ``_div2``, ``_cg_update2``, ``_precond2``): each system carries the bits and the
+        count of the single-system preconditioned solve."""
+        ctx, lay, PB = self.ctx, self.ctx.layout, self.PARTIALS
+        out0_ptr = v0_ptr if out0_ptr is None else out0_ptr
+        out1_ptr = v1_ptr if out1_ptr is None else out1_ptr
+        w, minv, d, sv, st = self._pair_buffers(), self.op._minv, lay.ldim, lay.sv, ctx.stream
+        x, r, p, Ep, z = ([a[0].data_ptr(), a[1].data_ptr()] for a in (w["x"], w["r"], w["p"], w["Ep"], w["z"]))
+        tp = [w["t"].data_ptr(), w["t"].data_ptr() + 8 * d * sv]
+        redp = w["red"].data_ptr()
+        inv_n, closed = 1.0 / max(self.npz_global, 1), int(self.closed)
+
+        def div2(u0, u1, ustride, mult, active):
+            ctx.call("nkv_pressure_div2", *self._head, u0, u1, ustride, mult, *Ep, *p, redp, active, st)
+
+        def update_precond2(red, Br, rz_ptr, Bo, buf, init, active):
+            ctx.call_nl("nkv_pressure_cg_update2", self.npz, *x, *r, *p, *Ep, None if red is None else red.data_ptr(),
+                        Br, rz_ptr, Bo, inv_n, closed, int(init), buf.data_ptr(), active, st)
+            ctx.call_nl("nkv_pressure_precond2", *self._fdm_head, *r, *z, buf.data_ptr() + 8 * 2 * PB, active, st)
+            return self._reduced2(buf, 3)                            # rows r.r, r.z, sum z: 2 Bo values each
+
+        # b = Z D v; x = 0, r = b, z = M r
+        div2(v0_ptr, v1_ptr, stride, None, 3)
+        red, Br = self._reduced2(w["red"], 3)
+        cur, Bo = update_precond2(red, Br, None, 1, w["pz"][0], True, 3)
+        bb = self._host_sums2(cur[: 2 * Bo], Bo)
+        if not all(math.isfinite(b) for b in bb):
+            raise RuntimeError("DivergenceFreeProjector: the divergence of the input is not finite")
+        stop = [(self.tol ** 2) * b for b in bb]
+        its = [0, 0]
+        active = sum(1 << s for s in range(2) if bb[s] > 0.0)
+        it, prev = 0, None
+        while active:
+            if it >= self.maxiter:
+                self.last_iterations_each, self.last_iterations = tuple(its), max(its)
+                now = self._host_sums2(cur[: 2 * Bo], Bo)
+                rel = max(math.sqrt(max(now[s], 0.0) / bb[s]) for s in range(2) if active >> s & 1)
+                raise RuntimeError(f"DivergenceFreeProjector: CG did not reach tol={self.tol:g} in maxiter={self.maxiter} "
+                                   f"iterations (|r|/|b| = {rel:.3e})")
+            ctx.call("nkv_pressure_pgradt2", *self._head, *p, *z, cur.data_ptr() + 8 * 2 * Bo,
+                     None if prev is None else prev.data_ptr() + 8 * 2 * Bo,
+                     cur.data_ptr() + 8 * 4 * Bo if closed else None, Bo, inv_n, int(it == 0), *tp, sv, active, st)
+            average_segments(self.op.face_average, w["t_sets"][active])
+            div2(*tp, sv, minv.data_ptr(), active)
+            red, Br = self._reduced2(w["red"], 3)
+            prev = cur
+            cur, Bo = update_precond2(red, Br, cur.data_ptr() + 8 * 2 * Bo, Bo, w["pz"][(it + 1) % 2], False, active)
+            it += 1
+            for s in range(2):
+                if active >> s & 1:
+                    its[s] = it
+            if it % self.check_every == 0:
+                now = self._host_sums2(cur[: 2 * Bo], Bo)
+                for s in range(2):
+                    if not active >> s & 1:
+                        continue
+                    if not math.isfinite(now[s]):
+                        raise RuntimeError("DivergenceFreeProjector: the CG residual is not finite")
+                    if now[s] <= stop[s]:
+                        active &= ~(1 << s)
+        self.last_iterations_each, self.last_iterations = tuple(its), max(its)
+        # out = v - minv dsavg(D^T x)   (x = 0 when b = 0: out = v)
+        ctx.call("nkv_pressure_gradt2", *self._head, *x, None, None, None, None, 1, 1, *tp, sv, 3, st)
+        average_segments(self.op.face_average, w["t_sets"][3])
         for v_ptr, t_ptr, o_ptr in ((v0_ptr, tp[0], out0_ptr), (v1_ptr, tp[1], out1_ptr)):
             ctx.call("nkv_advdiff_stage", v_ptr, stride, minv.data_ptr(), t_ptr, sv, -1.0, o_ptr, stride, d, 0, st)
 
